@@ -12,13 +12,18 @@ Workload = BASELINE.json configs[1]-class headline "5-way 5-shot Conv4" shape th
 (N=105, D=1600, C=5); inputs (normalised features Z) are resident in HBM before the timed
 region.  Episodes shard across ranks with no data-path collective (weak scaling).
 
-  python bench.py [--gpus N --steps K --warmup W --episodes B --config cfg2]
+  python bench.py [--gpus N --steps K --warmup W --episodes B --config cfg2 --dump-outputs DIR --full]
       N > 1 without a launcher: bench.py spawns the N ranks itself (one process per GPU, RCCL).
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Timing: W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + torch.cuda.synchronize()
-on both sides, MAX over ranks; blocks repeat until >= 1 s has been timed (at least 3) and the MEDIAN block is
-reported (`timing` holds min / max / count).  Prints ONE JSON line on rank 0.
+Timing: W warm-up steps, then ONE block of exactly K steps bracketed by barrier + torch.cuda.synchronize() on
+both sides, MAX over ranks; `ms_per_step` = block / K.  Prints ONE JSON line on rank 0.
+
+A plain run does only that (plus the per-kernel times and rooflines of the same block).  --full adds everything
+else: the other BASELINE configs, the batch-size sweep, the exact-fp32 twin run, the other entry paths, the
+test-time episode, the oracle check, the CPU baselines, the determinism check of the headline step, the timed
+collective alone (N > 1) and the detail file.  --dump-outputs DIR writes what the last timed step returned
+(`_dump_outputs`); the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -105,6 +110,11 @@ def _cgroup_cpu_quota():
         return None
 
 
+# Worker processes of the all-cores baseline.  Each imports the ROCm build of torch, which counts as a process with the GPU open even with no
+# device visible; with the bench process itself that makes at most 16, the most a shared GPU node admits.
+BASELINE_MAX_PROCS = 15
+
+
 def _usable_cores():
     """(cpu ids this process may run on -- one per PHYSICAL core where the SMT topology is readable --, facts dict).  The all-cores baseline
     starts one pinned single-thread process per entry, capped by the cgroup quota."""
@@ -123,9 +133,10 @@ def _usable_cores():
             cpus.append(cpu)
     quota = _cgroup_cpu_quota()
     facts = {"host_cpus": os.cpu_count(), "affinity_cpus": len(aff), "physical_cores_in_affinity": len(cpus), "physical_cores_psutil": _physical_cores(),
-             "cgroup_cpu_quota": quota}
+             "cgroup_cpu_quota": quota, "process_cap": BASELINE_MAX_PROCS}
     if quota is not None:
         cpus = cpus[:max(1, int(quota))]
+    cpus = cpus[:BASELINE_MAX_PROCS]
     facts["cores_effective"] = len(cpus)
     return cpus, facts
 
@@ -216,7 +227,7 @@ def cpu_baseline(z_cpu, n_way, raw_s, mean, warm=20, timed=200, repeats=5, windo
     backward), B = 1 sequential episodes as the reference runs them, on this box's host cores:
       * `1`: one process, one thread: `warm` untimed + `timed` timed episodes, median of up to `repeats` (<= 10 s);
       * `all_cores`: P = `cores_effective` independent single-thread PROCESSES (one per physical core of this process's affinity mask,
-        capped by the cgroup CPU quota; each pinned to its core, OMP / MKL_NUM_THREADS = 1), each running its own sequential episode
+        capped by the cgroup CPU quota and at BASELINE_MAX_PROCS; each pinned to its core, OMP / MKL_NUM_THREADS = 1), each running its own sequential episode
         stream; the episodes all of them complete inside `windows` shared wall-clock windows of `window_s` seconds, summed (median
         window).  This is the fair "all host cores" denominator: one B = 1 stream cannot use 128 threads (round 3 timed exactly that and
         got 22 x LESS than one thread)."""
@@ -381,7 +392,8 @@ def _workload(cfg, b, dev, rank, unit_rows):
             loss = obj.mean()
             loss.backward()
             return loss, logp, info
-        return step, dict(z=z, y=y, raw_s=raw_s, mean=mean, params=params, c=c, s=s, q=q, n=n, d=d, desc=desc, n_backbone=n_backbone, kernel="rbf")
+        return step, dict(z=z, y=y, raw_s=raw_s, mean=mean, params=params, param_names=("raw_outputscale", "mean", "raw_lengthscale", "raw_noise"), c=c, s=s, q=q, n=n, d=d,
+                          desc=desc, n_backbone=n_backbone, kernel="rbf")
     z = synthetic_batch(b, n, d, 1234 + rank, dev).requires_grad_(True)
     noise = torch.full((c,), 0.1, device=dev)
     cls = torch.arange(c, device=dev).repeat_interleave(s + q)
@@ -399,8 +411,8 @@ def _workload(cfg, b, dev, rank, unit_rows):
         loss = obj.mean()
         loss.backward()
         return loss, logp, info
-    return step, dict(z=z, y=y, raw_s=raw_s, mean=mean, noise=noise, params=[raw_s, mean], c=c, s=s, q=q, n=n, d=d, desc=desc,
-                      n_backbone=n_backbone, kernel="bncossim")
+    return step, dict(z=z, y=y, raw_s=raw_s, mean=mean, noise=noise, params=[raw_s, mean], param_names=("raw_outputscale", "mean"), c=c, s=s, q=q, n=n, d=d,
+                      desc=desc, n_backbone=n_backbone, kernel="bncossim")
 
 
 def _aux_paths(dev, cfg="cfg2", b=2048, b_rbf=None, steps=20, only=None):
@@ -522,9 +534,10 @@ def _algorithmic(cfg, n, d, c, unit_rows, lowrank=False):
     return alg
 
 
-def _measure(cfg, b, args, dev, rank, world, bucket_fn, unit_rows, min_blocks, min_total, steps, ktime=True):
+def _measure(cfg, b, args, dev, rank, world, bucket_fn, unit_rows, min_blocks, min_total, steps, ktime=True, check_det=True, after_timing=None):
     """Warm-up, then blocks of EXACTLY `steps` steps bracketed by barrier + synchronize on both sides (MAX over ranks), at least
-    `min_blocks` blocks and `min_total` seconds; per-kernel HIP-event times from the same blocks.  Returns the measurement dict."""
+    `min_blocks` blocks and `min_total` seconds; per-kernel HIP-event times from the same blocks.  `after_timing(loss, logp, info, st)` sees
+    the last timed step's results before anything else runs; `check_det` adds two untimed steps (determinism).  Returns the measurement dict."""
     from dkt_amd import ops
     step0, st = _workload(cfg, b, dev, rank, unit_rows)
     bucket = bucket_fn(st)
@@ -567,14 +580,48 @@ def _measure(cfg, b, args, dev, rank, world, bucket_fn, unit_rows, min_blocks, m
     # one block -- an allocation, a clock ramp after the previous config -- does not leak into the reported kernel time)
     ktimes = {name: (sum(cn for cn, _ in v), statistics.median(ms for _, ms in v)) for name, v in ktimes_all.items()}
     ok = int(info.abs().max().item()) == 0 and bool(torch.isfinite(loss))
-    # same inputs -> bitwise the same outputs (no atomics, fixed reduction orders): a hand-off race in a kernel would
-    # show up here as a handful of differing episodes
-    _, logp_a, _ = step()
-    grad_a = st["z"].grad.clone()
-    _, logp_b, _ = step()
-    deterministic = bool(torch.equal(logp_a, logp_b)) and bool(torch.equal(grad_a, st["z"].grad))
-    return dict(st=st, bucket=bucket, step=step, dt=dt, blocks=blocks, total=total, ktimes=ktimes, valid=ok and deterministic,
+    if after_timing is not None:
+        after_timing(loss, logp, info, st)
+    deterministic = None
+    if check_det:
+        # same inputs -> bitwise the same outputs (no atomics, fixed reduction orders): a hand-off race in a kernel would
+        # show up here as a handful of differing episodes
+        _, logp_a, _ = step()
+        grad_a = st["z"].grad.clone()
+        _, logp_b, _ = step()
+        deterministic = bool(torch.equal(logp_a, logp_b)) and bool(torch.equal(grad_a, st["z"].grad))
+    return dict(st=st, bucket=bucket, step=step, dt=dt, blocks=blocks, total=total, ktimes=ktimes, valid=ok and deterministic is not False,
                 deterministic=deterministic, logp=logp, steps=steps, b=b)
+
+
+DUMP_SAMPLE_SEED = 20240917        # the fixed episode sample of the dZ dump
+DUMP_SAMPLE_EPISODES = 32
+DUMP_SAMPLE_BYTES = 32 << 20       # dZ sample budget; the per-episode [B, C] arrays are sampled the same way above DUMP_ROWS_BYTES
+DUMP_ROWS_BYTES = 8 << 20
+
+
+def _dump_outputs(out_dir, loss, logp, info, st):
+    """--dump-outputs: what a caller of the timed step receives from its LAST timed step, one float32 .npy file each (< 64 MB in all):
+    loss [1], logp [B, C], info [B, C] (the factorisation failure flags), grad_<parameter> [C] (the hyper-parameter gradients; at N > 1 GPUs
+    after the step's all-reduce) and dz_sample [k, N, D] = dL/dZ of a fixed seeded sample of k <= 32 episodes (sorted indices of
+    torch.randperm(B) seeded with DUMP_SAMPLE_SEED; all of them when B <= k).  The inputs are seeded, so the files of two runs with the same
+    arguments compare output for output.  Returns the file names."""
+    import numpy as np
+    z = st["z"]
+    b = int(z.shape[0])
+    k = max(1, min(b, DUMP_SAMPLE_EPISODES, DUMP_SAMPLE_BYTES // (4 * z[0].numel())))
+    idx = torch.arange(b) if k == b else torch.randperm(b, generator=torch.Generator().manual_seed(DUMP_SAMPLE_SEED))[:k].sort().values
+
+    def rows(t):
+        t = t.detach()
+        return t if 4 * t.numel() <= DUMP_ROWS_BYTES else t[idx.to(t.device)]
+    arrays = {"loss": loss.detach().reshape(1), "logp": rows(logp), "info": rows(info), "dz_sample": z.grad[idx.to(z.device)]}
+    for name, p in zip(st["param_names"], st["params"]):
+        arrays["grad_" + name] = p.grad
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().cpu().to(torch.float32).numpy())
+    return sorted(arrays)
 
 
 def _traffic_table():
@@ -821,10 +868,16 @@ def run(args):
         return bkt
 
     b = args.episodes or _default_batch(args.config)
-    m = _measure(args.config, b, args, dev, rank, world, bucket_fn, UNIT_ROWS, 3, 1.0, args.steps)
+    dumped = []
+
+    def dump(loss_, logp_, info_, st_):
+        dumped.extend(_dump_outputs(args.dump_outputs, loss_, logp_, info_, st_))
+    # the headline: ONE block of exactly --steps timed steps
+    m = _measure(args.config, b, args, dev, rank, world, bucket_fn, UNIT_ROWS, 1, 0.0, args.steps, check_det=args.full,
+                 after_timing=dump if (args.dump_outputs and rank == 0) else None)
     st, bucket, dt, blocks, total = m["st"], m["bucket"], m["dt"], m["blocks"], m["total"]
     z, raw_s, mean, logp, step = st["z"], st["raw_s"], st["mean"], m["logp"], m["step"]
-    ar_ms = _allreduce_ms(bucket, world, dev) if world > 1 else 0.0
+    ar_ms = _allreduce_ms(bucket, world, dev) if (world > 1 and args.full) else 0.0
 
     if rank == 0:
         eps = world * b * args.steps / dt
@@ -853,7 +906,9 @@ def run(args):
             "roofline_by_kernel": roofline_all, "kernels": kernels,
             "collective": _collective_info(bucket, world, ar_ms, backend),
         }
-    if world == 1 and not args.no_other_configs:
+        if args.dump_outputs:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if args.full and world == 1 and not args.no_other_configs:
         # every other BASELINE config under the same clock (3 blocks each): value, ms_per_step, per-kernel rooflines
         others = {}
         for cfg in sorted(CONFIGS):
@@ -908,7 +963,7 @@ def run(args):
         out["other_paths_cfg1"] = _aux_paths(dev, "cfg1", 8192, 2048, 10)          # the Omniglot shape from trunk features: the feature-space episode behind the streaming front end
         torch.cuda.empty_cache()
     if rank == 0:
-        if world == 1 and not args.no_test_time and args.config != "cfg0":
+        if args.full and world == 1 and not args.no_test_time and args.config != "cfg0":
             # the forward-only test-time episode (`correct`, DKT.py:199-272) reported separately:
             # condition on the 25 support features, predict the 75 queries (Gram, MLL without gradients, cross Gram, mean + arg-max)
             noise = st["noise"]
@@ -938,7 +993,7 @@ def run(args):
                                         "ms_per_step": round(1e3 * dt_t, 4),
                                         "workload": "N_support=%d, N_query=%d, D=%d, C=%d: Gram + MLL (no grad) + cross Gram + posterior mean/arg-max"
                                                     % (c * s, c * q, d, c)}
-        if world == 1 and (not args.no_cpu_baseline or args.oracle_check) and args.config != "cfg0":
+        if world == 1 and ((args.full and not args.no_cpu_baseline) or args.oracle_check) and args.config != "cfg0":
             import numpy as np
             from oracle import dkt_oracle as O
             nchk = 32                                         # marginal log-likelihood of 32 bench episodes against the float64 oracle
@@ -951,7 +1006,7 @@ def run(args):
                 rel = max(rel, float(np.abs((logp[i].cpu().numpy() - ref["logp"]) / ref["logp"]).max()))
             out["mll_rel_err"] = rel
             out["mll_rel_err_episodes"] = nchk
-        if world == 1 and not args.no_cpu_baseline and args.config != "cfg0":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config != "cfg0":
             zs_cpu = z[:32].detach().cpu()
             res = cpu_baseline(zs_cpu, c, raw_s.detach().cpu(), mean.detach().cpu())
             one = res["1"]["episodes_per_s"]
@@ -962,8 +1017,8 @@ def run(args):
                                    "sample": "fp32 torch-CPU GPyTorch-structured port of the same training episode (per-class loop, Cholesky, autograd "
                                              "backward), B=1 sequential streams over 32 distinct synthetic Z.  one_thread: 20 warm-up + 200 timed episodes, "
                                              "median of up to 5 repeats (<= 10 s).  all_cores: one pinned single-thread process per effective core "
-                                             "(physical cores of the affinity mask, capped by the cgroup CPU quota), episodes all of them completed inside 3 "
-                                             "shared 3-s windows, summed.  value = the larger of the two",
+                                             "(physical cores of the affinity mask, capped by the cgroup CPU quota and at %d processes), episodes all of them completed inside 3 "
+                                             "shared 3-s windows, summed.  value = the larger of the two" % BASELINE_MAX_PROCS,
                                    "one_thread": one, "all_cores": allc, "cores_effective": facts["cores_effective"],
                                    "parallel_efficiency": res.get("all_cores", {}).get("parallel_efficiency"),
                                    "slowest_process_eps": res.get("all_cores", {}).get("slowest_process_eps"),
@@ -987,7 +1042,8 @@ def run(args):
     if world > 1:
         torch.distributed.destroy_process_group()
     if rank == 0:
-        out["detail"] = _write_detail(out)
+        if args.full:
+            out["detail"] = _write_detail(out)
         _emit(real_stdout, _line_of(out))
 
 
@@ -1019,11 +1075,11 @@ def _graphed_step_ms(cfg, b, dev, rank, unit_rows, reps=300):
 
 
 def _exact_fp32_run(args):
-    """`bench.py --config <headline> --no-other-configs --no-cpu-baseline --no-test-time` in a child with DKT_TWINS=1 DKT_GRAM_SPLIT=0 DKT_MLL_F32MFMA=1: value, ms per step,
-    per-kernel ms and the log-likelihood error of the exact-fp32 twin kernels on the same step."""
+    """`bench.py --config <headline> --oracle-check` (a plain run: the headline step alone, 100 timed steps) in a child with DKT_TWINS=1 DKT_GRAM_SPLIT=0
+    DKT_MLL_F32MFMA=1: value, ms per step, per-kernel ms and the log-likelihood error of the exact-fp32 twin kernels on the same step."""
     import subprocess
     env = dict(os.environ, DKT_TWINS="1", DKT_GRAM_SPLIT="0", DKT_MLL_F32MFMA="1")
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", args.config, "--steps", "10", "--warmup", "2", "--no-other-configs", "--no-cpu-baseline", "--no-test-time", "--oracle-check"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", args.config, "--steps", "100", "--warmup", "10", "--oracle-check"]
     try:
         res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
         rec = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -1058,7 +1114,7 @@ def _line_of(out):
                          for name, o in out[key].items()}
     if "test_time_forward" in out:
         line["test_time_forward"] = {k: out["test_time_forward"][k] for k in ("value", "ms_per_step", "episodes_per_step")}
-    for k in ("mll_rel_err", "mll_rel_err_episodes", "speedup_vs_cpu", "speedup_vs_cpu_1thread", "gpytorch_reference", "rccl_selftest", "detail", "batch_sweep", "exact_fp32"):
+    for k in ("mll_rel_err", "mll_rel_err_episodes", "speedup_vs_cpu", "speedup_vs_cpu_1thread", "gpytorch_reference", "rccl_selftest", "detail", "batch_sweep", "exact_fp32", "dump_outputs"):
         if k in out:
             line[k] = out[k]
     if "cpu_baseline" in out:
@@ -1172,10 +1228,15 @@ def main():
     ap.add_argument("--episodes", type=int, default=None,
                     help="episodes per step per GPU (SURVEY.md 8d: B in {1, 64, 1024, 8192}); default 8192, 1024 for the 20-way shapes")
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the other BASELINE configs, batch sweep, exact-fp32 twins, other entry paths, test-time "
+                         "episode, oracle check, CPU baselines, determinism check, collective timing, detail file (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, < 64 MB; dZ as a fixed seeded sample of episodes)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--oracle-check", action="store_true", help="with --no-cpu-baseline: still check 32 bench episodes against the float64 oracle (mll_rel_err)")
+    ap.add_argument("--oracle-check", action="store_true", help="check 32 bench episodes against the float64 oracle (mll_rel_err) without --full too")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="only the --config workload (default: the headline config in full, then every other BASELINE config for 3 "
+                    help="with --full: only the --config workload (default: the headline config in full, then every other BASELINE config for 3 "
                          "short blocks each, reported under `other_configs`)")
     ap.add_argument("--no-test-time", action="store_true",
                     help="skip the separately reported forward-only test-time episode (profiling runs: keeps the per-kernel "
@@ -1186,6 +1247,8 @@ def main():
     ap.add_argument("--selftest-collective", action="store_true",
                     help="CPU-only (gloo) check of the multi-rank plumbing: spawn, rendezvous, the flat gradient bucket; no kernels")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: one process per GPU, spawned here (the driver's torch.distributed.run path sets WORLD_SIZE itself)
         import socket

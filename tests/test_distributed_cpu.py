@@ -241,6 +241,49 @@ def test_bench_line_stays_under_8k_with_every_section_filled():
     assert set(("value", "unit", "cores", "kind", "sample")) <= set(line["cpu_baseline"]) and "by_threads" not in line["cpu_baseline"]
 
 
+def _fake_bench_step(b, n, d, c, names, seed):
+    """CPU stand-in for the last timed step of bench.py: (loss, logp [B, C], info [B, C], state) with gradients on Z and the hyper-parameters."""
+    g = torch.Generator().manual_seed(seed)
+    z = torch.randn(b, n, d, generator=g).requires_grad_(True)
+    params = [torch.randn(c, generator=g).requires_grad_(True) for _ in names]
+    loss = (z * z).sum() * 0.5 + sum((p * p).sum() for p in params)
+    loss.backward()
+    logp = torch.randn(b, c, generator=g)
+    info = torch.zeros(b, c, dtype=torch.int32)
+    return loss, logp, info, dict(z=z, params=params, param_names=names)
+
+
+def test_bench_dump_outputs_are_float_files_of_a_fixed_sample_within_budget(tmp_path):
+    """--dump-outputs: the last timed step's results as float32 .npy files, < 64 MB in all; dZ of a large batch is a fixed seeded sample
+    of episodes (the same one from run to run), per-episode [B, C] arrays are sampled with the same episodes once they pass 8 MB."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    for b, n, d, c, names in ((100, 420, 512, 20, ("raw_outputscale", "mean")),                      # 20-way episode: the byte budget binds dZ
+                              (3, 19, 64, 1, ("raw_outputscale", "mean", "raw_lengthscale", "raw_noise")),  # fewer episodes than the sample: all of them
+                              (500000, 2, 2, 5, ("raw_outputscale", "mean"))):                     # logp / info above 8 MB: sampled too
+        loss, logp, info, st = _fake_bench_step(b, n, d, c, names, b)
+        files = {}
+        for rep in ("a", "b"):
+            names_out = bench._dump_outputs(str(tmp_path / ("%d%s" % (b, rep))), loss, logp, info, st)
+            assert set(names_out) == {"loss", "logp", "info", "dz_sample"} | {"grad_" + p for p in names}
+            files[rep] = {k: np.load(str(tmp_path / ("%d%s" % (b, rep)) / (k + ".npy"))) for k in names_out}
+        total = 0
+        for k, a in files["a"].items():
+            assert a.dtype == np.float32 and np.array_equal(a, files["b"][k]), k
+            total += a.nbytes
+        assert total < 64 << 20
+        k_ep = files["a"]["dz_sample"].shape[0]
+        assert 1 <= k_ep <= min(b, 32)
+        idx = torch.arange(b) if k_ep == b else torch.randperm(b, generator=torch.Generator().manual_seed(bench.DUMP_SAMPLE_SEED))[:k_ep].sort().values
+        np.testing.assert_array_equal(files["a"]["dz_sample"], st["z"].grad[idx].numpy())
+        assert files["a"]["loss"].shape == (1,) and float(files["a"]["loss"][0]) == np.float32(loss.item())
+        np.testing.assert_array_equal(files["a"]["logp"], (logp if 4 * logp.numel() <= bench.DUMP_ROWS_BYTES else logp[idx]).numpy())
+        for p, name in zip(st["params"], names):
+            np.testing.assert_array_equal(files["a"]["grad_" + name], p.grad.numpy())
+
+
 def test_grad_bucket_zero_clears_gradients_that_are_not_views():
     """GradBucket.zero_() replaces optimizer.zero_grad() in distributed mode: besides the flat fp32 buffer it must clear the gradients that are
     not views of it (attach() leaves non-fp32 parameters alone), or they would accumulate from step to step."""

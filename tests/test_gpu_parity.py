@@ -3104,3 +3104,36 @@ def test_bench_line_is_last_on_stdout_with_rccl_initialised(cuda):
     assert out["valid"] and out["steps"] == 2 and out["warmup"] == 1 and out["config"]["workload"].startswith("cfg2")
     rc = out["rccl_selftest"]
     assert rc["valid"] and all(b["pack_copies"] == 0 and b["grads_are_views"] for b in rc["buckets"].values())
+
+
+def test_bench_plain_run_times_exactly_steps_and_dumps_the_same_outputs_twice(cuda, tmp_path):
+    """A plain `bench.py` run is the headline alone: ONE block of exactly --steps timed steps (ms_per_step = block / steps), none of the --full
+    sections.  --dump-outputs writes what the last timed step returned; two runs with the same arguments write the same arrays."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for rep in ("a", "b"):
+        d = str(tmp_path / rep)
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--episodes", "256",
+                              "--dump-outputs", d], capture_output=True, text=True, timeout=300, env=env)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = res.stdout.strip().splitlines()
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["valid"] and out["steps"] == 3 and out["timing"]["blocks"] == 1 and out["timing"]["steps_per_block"] == 3
+        assert abs(out["ms_per_step"] - 1e3 * out["timing"]["block_s_median"] / 3) < 1e-3 and out["ms_per_step"] > 0.0
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert key in out
+        for key in ("other_configs", "batch_sweep", "exact_fp32", "other_paths_cfg2", "test_time_forward", "cpu_baseline", "mll_rel_err", "detail"):
+            assert key not in out, key
+        names = out["dump_outputs"]["arrays"]
+        assert set(names) == {"loss", "logp", "info", "dz_sample", "grad_raw_outputscale", "grad_mean"}
+        dumps.append({k: np.load(os.path.join(d, k + ".npy")) for k in names})
+    a, b = dumps
+    assert a["logp"].shape == (256, 5) and a["dz_sample"].shape == (32, 105, 1600) and a["grad_mean"].shape == (5,)
+    assert (a["info"] == 0).all() and all(np.isfinite(v).all() for v in a.values())
+    for k in a:
+        assert a[k].dtype == np.float32
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)

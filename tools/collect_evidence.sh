@@ -7,8 +7,9 @@ timeout 400 python tools/check_band.py time > gpurun_out/band_final_check_band.l
 bash tools/prof_band.sh final > /dev/null 2>&1
 timeout 300 python tools/band_phase_clocks.py > gpurun_out/band_final_phase_clocks.log 2>&1
 timeout 1500 python -m pytest tests -m gpu -x -q > gpurun_out/final_pytest_gpu.log 2>&1; tail -2 gpurun_out/final_pytest_gpu.log
-timeout 700 python bench.py > gpurun_out/final_bench_line.json 2> gpurun_out/final_bench.err; wc -c gpurun_out/final_bench_line.json
-cp gpurun_out/bench_detail.json gpurun_out/final_bench_detail.json
+timeout 700 python bench.py --full > final_bench_line.json 2> final_bench.err; wc -c final_bench_line.json
+# the line and its logs next to the detail file the line names
+D=$(python -c "import json; print(json.load(open('final_bench_line.json'))['detail'].rsplit('/', 1)[0])"); mv final_bench_line.json final_bench.err "$D/"; cp "$D/bench_detail.json" "$D/final_bench_detail.json"
 bash tools/b1_minb_probe.sh > gpurun_out/b1_probe_final.log 2>&1
 bash tools/prof_b1.sh > /dev/null 2>&1
 python tools/b1_cpu_overhead.py 1 > gpurun_out/b1_cpu_overhead.log 2>&1
