@@ -117,20 +117,26 @@ _VARIANT_SWITCHES = ("DKT_GRAM_EP", "DKT_GRAM_SPLIT", "DKT_GRAM_EP_BK", "DKT_GRA
                      "DKT_GRAM_BWD_SPLIT_VAR", "DKT_GRAM_BWD_UNIT_MIND", "DKT_GRAM_BWD_SPLIT_MIND", "DKT_MLL_TILED_F16", "DKT_GRAM_DIST_EP", "DKT_MLL_P2_GUARD",
                      "DKT_MLL_TILED_WRES", "DKT_MLL_TILED_INVRES", "DKT_GRAM_BIG_EP", "DKT_MLL_TILED_WGS", "DKT_GRAM_BWD_ROWS8", "DKT_MLL_TILED_WDMA", "DKT_CLASS_BWD_V4",
                      "DKT_MLL_TILED_WNW", "DKT_GRAM_SMALL", "DKT_BIG_NB", "DKT_GRAM_BN_F16", "DKT_LDS_STAGE_OLD", "DKT_GRAM_SMALL_WG", "DKT_CLASS_BWD_N128", "DKT_GRAM_FEWEP",
-                     "DKT_GRAM_SMALL_XR", "DKT_GRAM_SMALL_LDS")
+                     "DKT_GRAM_SMALL_XR", "DKT_GRAM_SMALL_LDS",
+                     # bytes of untouched dynamic LDS on top of a kernel's own (occupancy A/B of the twins library, dkt_lds_pad)
+                     "DKT_PAD_AFFNORM", "DKT_PAD_BAND_BACK", "DKT_PAD_BAND_CLASS", "DKT_PAD_BAND_FWD", "DKT_PAD_CK_BWD", "DKT_PAD_CK_FWD", "DKT_PAD_FE_FWD",
+                     "DKT_PAD_GRAM_BIG_BWD", "DKT_PAD_GRAM_EP", "DKT_PAD_GRAM_EP_BWD", "DKT_PAD_LR_BWD", "DKT_PAD_LR_FIN", "DKT_PAD_LR_GRAM", "DKT_PAD_NBB",
+                     "DKT_PAD_ROWDOT")
 _ENV_SWITCHES = _PRODUCT_SWITCHES + _VARIANT_SWITCHES
-_env_seen = {}
+_env_seen = {}           # id(lib) -> {switch: value} as of the library's last (re)read of the environment
 
 
 def _sync_env(lib, names=None) -> None:
     """The library reads its switches once; when a test or an A/B tool changed one inside this process, tell it.  `names`: the switches that can matter for this
-    library (the product reads the 4 product switches only: ~ 4 instead of ~ 30 environment look-ups per call on the launch-bound small-batch paths)."""
-    cur = tuple(os.environ.get(k) for k in (names or _ENV_SWITCHES))
+    library (the product reads the 4 product switches only: ~ 4 instead of ~ 30 environment look-ups per call on the launch-bound small-batch paths).  The snapshot
+    is per library and covers every switch, whichever subset a call compares: a process that alternates the two name sets on the same library (DKT_TWINS toggled)
+    reloads only when a switch really changed."""
     seen = _env_seen.get(id(lib))
-    if cur != seen:
-        if seen is not None or any(v is not None for v in cur):
+    if seen is None or any(os.environ.get(k) != seen[k] for k in (names or _ENV_SWITCHES)):
+        snap = {k: os.environ.get(k) for k in _ENV_SWITCHES}
+        if seen is not None or any(v is not None for v in snap.values()):
             lib.dkt_reload_env()
-        _env_seen[id(lib)] = cur
+        _env_seen[id(lib)] = snap
 
 
 def _lib_now(want_twin: bool = False):

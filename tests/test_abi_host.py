@@ -148,6 +148,59 @@ def test_library_selection_product_unless_twins_are_asked_for(monkeypatch):
     assert ops._lib_now()._name == L.LIB_PATH
 
 
+def test_every_switch_the_twins_library_reads_is_routed():
+    """Every DKT_* name compiled into libdkt_twins.so is a switch ops knows: set alone with DKT_TWINS=1, a variant switch must send the call to the twins library
+    (the product ignores it without a word, and an A/B run would time the same kernel twice)."""
+    ops = dkt_amd.ops
+    blob = open(dkt_amd._lib.build_twins(), "rb").read()
+    found = set(m.decode() for m in re.findall(rb"(?<![A-Za-z0-9_])(DKT_[A-Z0-9_]+)\0", blob))
+    assert len(found) > 20
+    missing = sorted(found - set(ops._ENV_SWITCHES) - {"DKT_TWINS"})
+    assert not missing, "switches of libdkt_twins.so that ops._lib_now() does not route: %s" % missing
+
+
+def test_env_sync_reloads_only_when_a_switch_changed(monkeypatch):
+    """ops._sync_env: toggling DKT_TWINS between 1 and unset syncs the product library with two different name sets -- that alone must not call dkt_reload_env();
+    a changed switch must, whichever name set the next call compares (also when the change happened under the other set and was undone since)."""
+    ops = dkt_amd.ops
+
+    class Stub:
+        _name = "stub"
+        reloads = 0
+
+        def dkt_reload_env(self):
+            Stub.reloads += 1
+
+    stub = Stub()
+    monkeypatch.setattr(ops._lib, "load", lambda path=None: stub)
+    monkeypatch.setattr(ops, "_env_seen", {})
+    for k in ops._ENV_SWITCHES + ("DKT_TWINS",):
+        monkeypatch.delenv(k, raising=False)
+    for _ in range(3):
+        monkeypatch.delenv("DKT_TWINS", raising=False)
+        assert ops._lib_now() is stub
+        monkeypatch.setenv("DKT_TWINS", "1")
+        assert ops._lib_now() is stub
+    assert Stub.reloads == 0
+    monkeypatch.setenv("DKT_MLL_H2E_MINB", "7")                   # changed under the full name set
+    ops._lib_now()
+    assert Stub.reloads == 1
+    monkeypatch.delenv("DKT_TWINS")
+    ops._lib_now()
+    assert Stub.reloads == 1                                       # ... already synced: the product name set sees no change
+    monkeypatch.setenv("DKT_MLL_H2E_MINB", "8")                   # changed under the product name set, then back to 7 before the next full-set call
+    ops._lib_now()
+    assert Stub.reloads == 2
+    monkeypatch.setenv("DKT_MLL_H2E_MINB", "7")
+    monkeypatch.setenv("DKT_TWINS", "1")
+    ops._lib_now()
+    assert Stub.reloads == 3                                       # the library holds 8: it must re-read
+    ops._lib_now()
+    monkeypatch.delenv("DKT_TWINS")
+    ops._lib_now()
+    assert Stub.reloads == 3
+
+
 def test_per_class_path_sizes():
     """Which (N, C) the one-launch per-class path serves (ops.mll_per_class_supported mirrors dkt_mll_f32 with DKT_MLL_E_PER_CLASS and dkt_class_kernel_bwd_f32)."""
     ok = dkt_amd.ops.mll_per_class_supported

@@ -68,12 +68,23 @@ EP_SHAPES = [(64, 65, 36), (64, 75, 512), (70, 80, 1024), (64, 96, 100), (64, 10
              (64, 128, 160), (96, 100, 32)]
 
 
+def _on_product_library():
+    """Right before a kernel call of a test that claims the product library: the call really goes there (a renamed switch cannot quietly move it to the twins)."""
+    assert ops._lib_now()._name == dkt_amd._lib.LIB_PATH
+
+
 @pytest.mark.parametrize("b,n,d", EP_SHAPES)
-@pytest.mark.parametrize("split", ["1", "0"])
+@pytest.mark.parametrize("split", ["1", "0", "default"])
 def test_gram_episode_resident_kernels(cuda, b, n, d, split, monkeypatch):
-    monkeypatch.setenv("DKT_GRAM_SPLIT", split)
+    """split "1" / "0": the twins library's bf16-split / exact-fp32 kernels (DKT_GRAM_SPLIT); "default": no switch -- the product library's own dispatch."""
+    if split == "default":
+        monkeypatch.delenv("DKT_GRAM_SPLIT", raising=False)
+    else:
+        monkeypatch.setenv("DKT_GRAM_SPLIT", split)
     g = torch.Generator(device=cuda).manual_seed(n * 7 + d)
     z = torch.randn(b, n, d, generator=g, device=cuda) * torch.exp(2.0 * torch.randn(b, n, d, generator=g, device=cuda))
+    if split == "default":
+        _on_product_library()
     e = ops.gram(z)
     ref = torch.einsum("bnd,bmd->bnm", z.double(), z.double())
     mag = torch.einsum("bnd,bmd->bnm", z.double().abs(), z.double().abs())      # what fp32 rounding errors scale with
@@ -180,14 +191,21 @@ def test_gram_split_pipeline_variants_agree_bitwise(cuda, var, monkeypatch):
 
 
 @pytest.mark.parametrize("b,n,d", EP_SHAPES)
-@pytest.mark.parametrize("split", ["1", "0"])
+@pytest.mark.parametrize("split", ["1", "0", "default"])
 def test_gram_bwd_episode_resident_kernels(cuda, b, n, d, split, monkeypatch):
-    monkeypatch.setenv("DKT_GRAM_SPLIT", split)
-    monkeypatch.setenv("DKT_GRAM_BWD_SPLIT_MIND", "32")              # force the split kernel also at small D
+    """split "1" / "0" (twins library): the bf16-split kernel at every D / exact fp32; "default": the product library (exact fp32 below D = 1024, the split from there)."""
+    if split == "default":
+        monkeypatch.delenv("DKT_GRAM_SPLIT", raising=False)
+        monkeypatch.delenv("DKT_GRAM_BWD_SPLIT_MIND", raising=False)
+    else:
+        monkeypatch.setenv("DKT_GRAM_SPLIT", split)
+        monkeypatch.setenv("DKT_GRAM_BWD_SPLIT_MIND", "32")              # force the split kernel also at small D
     g = torch.Generator(device=cuda).manual_seed(n * 11 + d)
     z = torch.randn(b, n, d, generator=g, device=cuda)
     w = torch.randn(b, n, n, generator=g, device=cuda) * torch.exp(2.0 * torch.randn(b, n, n, generator=g, device=cuda))
     sc = torch.rand(b, generator=g, device=cuda) + 0.5
+    if split == "default":
+        _on_product_library()
     dz = ops.gram_bwd(w, z, sc)
     ws = (w + w.transpose(1, 2)).double() * sc.double().view(-1, 1, 1)
     ref = ws @ z.double()
@@ -278,13 +296,27 @@ def test_gram_unit_rows_promise_violation_is_loud(cuda):
 @pytest.mark.parametrize("b,n,d", EP_SHAPES)
 @pytest.mark.parametrize("kind", ["plain", "heavy"])
 def test_gram_bwd_unit_rows_f16_split(cuda, b, n, d, kind, monkeypatch):
-    monkeypatch.setenv("DKT_GRAM_BWD_UNIT_MIND", "32")               # force the split kernel also at D < 64
+    monkeypatch.setenv("DKT_GRAM_BWD_UNIT_MIND", "32")               # force the split kernel also at D < 64 (twins library)
+    _check_gram_bwd_unit_rows(cuda, b, n, d, kind, product=False)
+
+
+@pytest.mark.parametrize("b,n,d", EP_SHAPES)
+@pytest.mark.parametrize("kind", ["plain", "heavy"])
+def test_gram_bwd_unit_rows_f16_split_product_dispatch(cuda, b, n, d, kind, monkeypatch):
+    """The same checks with no switch set: the product library's own choice of kernel by D."""
+    monkeypatch.delenv("DKT_GRAM_BWD_UNIT_MIND", raising=False)
+    _check_gram_bwd_unit_rows(cuda, b, n, d, kind, product=True)
+
+
+def _check_gram_bwd_unit_rows(cuda, b, n, d, kind, product):
     z = _unit_rows(b, n, d, n * 17 + d, cuda, kind)
     g = torch.Generator(device=cuda).manual_seed(n + d)
     # gradient-like W: per-row AND per-entry dynamic range, one all-zero row, one tiny row
     w = torch.randn(b, n, n, generator=g, device=cuda) * torch.exp(2.0 * torch.randn(b, n, 1, generator=g, device=cuda)) \
         * torch.exp(1.5 * torch.randn(b, n, n, generator=g, device=cuda))
     sc = torch.rand(b, generator=g, device=cuda) + 0.5
+    if product:
+        _on_product_library()
     dz = ops.gram_bwd(w, z, sc, unit_rows=True)
     ws = (w + w.transpose(1, 2)).double() * sc.double().view(-1, 1, 1)
     ref = ws @ z.double()
@@ -297,6 +329,8 @@ def test_gram_bwd_unit_rows_f16_split(cuda, b, n, d, kind, monkeypatch):
     assert torch.equal(dz, ops.gram_bwd(w, z, sc, unit_rows=True)), "deterministic"
     w0 = torch.zeros_like(w)
     w0[:, 3, 7] = 1e-30
+    if product:
+        _on_product_library()
     dz0 = ops.gram_bwd(w0, z, None, unit_rows=True)      # all-zero rows and a denormal-scale row: finite, exact zeros elsewhere
     assert torch.isfinite(dz0).all() and (dz0[:, 0] == 0).all()
     assert (dz0[:, 3].double() - 1e-30 * z[:, 7].double()).abs().max().item() < 1e-36
@@ -357,13 +391,18 @@ def test_mll_forward_and_gradients_vs_oracle(cuda, c, per, d, corr, path, monkey
     generic LDS / global kernel for every N."""
     force_generic, force_reg, force_f32 = path == "generic", path == "reg", path == "f32mfma"
     want_chol = path not in ("default", "h2e", "h2e_grow")
-    monkeypatch.setenv("DKT_MLL_H2E_MINB", "1" if path.startswith("h2e") else "1000000000")
-    monkeypatch.setenv("DKT_MLL_P2_GUARD", "-1" if path == "h2e_grow" else "1")
+    monkeypatch.setenv("DKT_MLL_H2E_MINB", "1" if path.startswith("h2e") else "1000000000")      # (a product switch)
+    if path == "h2e_grow":
+        monkeypatch.setenv("DKT_MLL_P2_GUARD", "-1")                  # (a variant switch: the twins library)
+    else:
+        monkeypatch.delenv("DKT_MLL_P2_GUARD", raising=False)
     z, hyp, n = _episode_case(c, per, d, 17 + n_hash(c, per, d), corr)
     y = O.one_vs_rest_targets(c, per)
     sv = hyp.outputscale
     cw = np.full(c, -1.0 / (c * n))
     e_dev = ops.gram(dev_t(z, cuda))
+    if path in ("default", "h2e", "generic"):
+        _on_product_library()
     out = ops.mll(e_dev, dev_t(y, cuda), dev_t(sv, cuda), dev_t(hyp.mean, cuda), dev_t(hyp.noise, cuda),
                   want_grad=True, want_chol=want_chol, cls_weight=dev_t(cw, cuda), force_generic=force_generic, force_reg=force_reg,
                   force_f32mfma=force_f32)
@@ -674,15 +713,18 @@ def test_mll_regression_head_noise_at_its_lower_bound_takes_the_exact_kernel(cud
             assert worst["logp"] < MLL_RTOL and worst["alpha"] < 5e-4 and worst["w"] < GRAD_RTOL, worst
 
 
-@pytest.mark.parametrize("guard", ["1", "0", "-1"])
+@pytest.mark.parametrize("guard", ["1", "0", "-1", "default"])
 def test_mll_wave_per_episode_class_weights_signs_and_units(cuda, monkeypatch, guard):
     """The wave-per-episode kernel (csrc/dkt_mll_h2.hip, mll_h2e_kernel) accumulates W over the classes inside the phase-3 products: the
     class weight is folded into the split scale, the accumulators carry one sign and one power-of-two unit.  Class weights of both signs,
     a zero weight, output scales three orders of magnitude apart (the unit grows from class to class) and C = 1 / 7 must reproduce the
     oracle, bitwise symmetrically and reproducibly -- at the default head room of the f16 scale of M (guard 1), without head room (0) and
-    through the grow-on-demand path on every matrix (-1)."""
+    through the grow-on-demand path on every matrix (-1) -- those three on the twins library --, and on the product library (default: no switch)."""
     monkeypatch.setenv("DKT_MLL_H2E_MINB", "1")
-    monkeypatch.setenv("DKT_MLL_P2_GUARD", guard)
+    if guard == "default":
+        monkeypatch.delenv("DKT_MLL_P2_GUARD", raising=False)
+    else:
+        monkeypatch.setenv("DKT_MLL_P2_GUARD", guard)
     rng = np.random.default_rng(11)
     for (c, per, d) in ((5, 21, 64), (7, 9, 32), (1, 40, 16), (3, 37, 24)):
         n = c * per
@@ -694,6 +736,8 @@ def test_mll_wave_per_episode_class_weights_signs_and_units(cuda, monkeypatch, g
         cw = np.array([-0.01, 0.02, 0.0, -0.3, 0.004, 0.05, -0.01])[:c]
         e_dev = ops.gram(dev_t(z, cuda))
         args = (e_dev, dev_t(y, cuda), dev_t(sv, cuda), dev_t(mean, cuda), dev_t(noise, cuda))
+        if guard == "default":
+            _on_product_library()
         out = ops.mll(*args, want_grad=True, cls_weight=dev_t(cw, cuda))
         again = ops.mll(*args, want_grad=True, cls_weight=dev_t(cw, cuda))
         torch.cuda.synchronize()
@@ -1418,6 +1462,173 @@ def test_mll_band_reduction_dispatch_window_and_condition_guard(cuda):
     assert abs(o["logp"][0, 5].item() - logp) < MLL_RTOL * abs(logp)
 
 
+# ----------------------------------------------------------------------------------------------
+# the guard fix-ups of the default dispatch: flagged and clean units mixed in one call, at the batch sizes that pick the guarded paths
+# ----------------------------------------------------------------------------------------------
+_MLL_KEYS = ("logp", "alpha", "w", "dsv", "dmean", "dnoise", "jitter", "info")
+
+
+def _unit_rows_gram(b, n, d, seed, scaled, cuda, per_class=0):
+    """Gram matrices of unit rows (the reference's normalised features), [B,N,N] -- or [B,C,N,N] with `per_class` = C --; the rows of the units in `scaled` (episode
+    indices, or (episode, class) pairs) are multiplied by 3, their trace by 9: over the fix-up's a-priori bound 1 + sv trace(E) / noise where the others stay under it."""
+    g = torch.Generator(device=cuda).manual_seed(seed)
+    z = torch.nn.functional.normalize(torch.randn(b * max(per_class, 1), n, d, generator=g, device=cuda), dim=2)
+    z = z.view(b, per_class, n, d) if per_class else z
+    for u in scaled:
+        z[u] *= 3.0
+    e = ops.gram(z.reshape(-1, n, d).contiguous())
+    return e.view(b, per_class, n, n) if per_class else e
+
+
+def _mll_vs_float64(o, e, y, sv, mean, noise, cw, i, per_class=False):
+    """Episode i of ops.mll's outputs against the float64 closed forms (K_c = sv_c E + noise_c I): logp per class, alpha, W (bitwise symmetric), the hyper-parameter
+    gradients (unweighted, as the ABI returns them)."""
+    c, n = len(sv), e.shape[-1]
+    w_ref = np.zeros((c, n, n)) if per_class else np.zeros((n, n))
+    hyper = ([], [], [])
+    for k in range(c):
+        ek = (e[i, k] if per_class else e[i]).double().cpu().numpy()
+        kk = sv[k] * ek + noise[k] * np.eye(n)
+        r = y[k] - mean[k]
+        kinv = np.linalg.inv(kk)
+        alpha = kinv @ r
+        logp = -0.5 * r @ alpha - 0.5 * np.linalg.slogdet(kk)[1] - 0.5 * n * np.log(2 * np.pi)
+        assert abs(o["logp"][i, k].item() - logp) < MLL_RTOL * abs(logp), (i, k, o["logp"][i, k].item(), logp)
+        assert rel_l2(o["alpha"][i, k].cpu().numpy(), alpha) < 5e-4, (i, k)
+        m = 0.5 * (np.outer(alpha, alpha) - kinv)
+        if per_class:
+            w_ref[k] = cw[k] * sv[k] * m
+        else:
+            w_ref += cw[k] * sv[k] * m
+        hyper[0].append((m * ek).sum()); hyper[1].append(np.trace(m)); hyper[2].append(alpha.sum())
+    wk = o["w"][i].cpu().numpy()
+    assert rel_l2(wk, w_ref) < GRAD_RTOL, (i, rel_l2(wk, w_ref))
+    assert (wk == np.swapaxes(wk, -1, -2)).all()
+    for key, ref in zip(("dsv", "dnoise", "dmean"), hyper):
+        assert rel_l2(o[key][i].cpu().numpy(), np.array(ref)) < GRAD_RTOL, (i, key)
+
+
+def _assert_units_equal(o, ref, sel_o, sel_ref=slice(None)):
+    for key in _MLL_KEYS:
+        assert torch.equal(o[key][sel_o], ref[key][sel_ref]), key
+
+
+def test_mll_band_reduction_condition_guard_fixup_mixed_batch(cuda):
+    """The band path's guard (dkt_mll_band.hip, dkt_mll_band_launch): an episode whose bound 1 + sv trace(E) / noise exceeds 2e4 is redone by the generic global kernel
+    on its own matrix, one pass per 1024-episode chunk.  cfg4's shape at the bench's batch (N = 420, C = 20, default dispatch: band from 192 episodes): one full chunk +
+    a ragged chunk of 6, every 8th episode or so scaled over the bound -- one of them in the tail chunk, where the fix-up runs at b0 = 1024.  Flagged episodes equal the
+    generic kernel on the same episodes alone bit for bit, clean ones the raw band reduction on the clean episodes alone; float64 spot checks in both chunks."""
+    b, n, c, d = 1030, 420, 20, 128
+    rng = np.random.default_rng(4200)
+    flagged = sorted(set(rng.choice(1024, 127, replace=False).tolist()) - {0, 1023} | {1026})
+    clean = sorted(set(range(b)) - set(flagged))
+    e = _unit_rows_gram(b, n, d, 42, flagged, cuda)
+    hyp = O.perturbed_hypers(c, 9)
+    y, sv, mean, noise = O.one_vs_rest_targets(c, n // c), hyp.outputscale, hyp.mean, hyp.noise
+    cw = np.full(c, -1.0 / (c * n))
+    # (unit rows: trace(E) = 420 -> bound <= 1 + 1.51 * 420 / 0.1 = 6.3e3; scaled: 9 x 420 -> up to 5.7e4: over 2e4 for every class with sv > 0.53)
+    tr = torch.diagonal(e, dim1=1, dim2=2).sum(1).double().cpu().numpy()
+    bound = 1.0 + np.max(sv) * tr / 0.1
+    assert (bound[flagged] > 2e4).all() and (bound[clean] < 1e4).all()
+    rest = [dev_t(x, cuda) for x in (y, sv, mean, noise)]
+    cwt = dev_t(cw, cuda)
+    torch.cuda.synchronize()
+    _on_product_library()
+    o = ops.mll(e, *rest, want_grad=True, cls_weight=cwt)
+    torch.cuda.synchronize()
+    assert int(o["info"].abs().max().item()) == 0 and float(o["jitter"].abs().max().item()) == 0.0
+    assert torch.equal(o["w"], o["w"].transpose(1, 2))
+    fi, ci = torch.tensor(flagged, device=cuda), torch.tensor(clean, device=cuda)
+    gen = ops.mll(e[fi].contiguous(), *rest, want_grad=True, cls_weight=cwt, force_generic=True)
+    _assert_units_equal(o, gen, fi)
+    del gen
+    raw = ops.mll(e[ci].contiguous(), *rest, want_grad=True, cls_weight=cwt, force_band=True)
+    _assert_units_equal(o, raw, ci)
+    del raw
+    for i in sorted({0, 1023, 1024, 1029, flagged[0], flagged[-2], flagged[-1], clean[1], 1025}):
+        _mll_vs_float64(o, e, y, sv, mean, noise, cw, i)
+
+
+def test_mll_f16_split_condition_guard_fixup_mixed_batch(cuda, monkeypatch):
+    """The f16-split kernels' guard (dkt_mll.hip, mll_kappa_fixup): a class whose bound 1 + sv trace(E) / noise exceeds 5e3 flags its episode, and the generic kernel
+    redoes the whole episode.  N = 105, C = 5 at 2048 episodes -- the wave-per-episode kernel of the default dispatch (DKT_MLL_H2E_MINB at its default 1024) --, and
+    the same inputs through the wave-per-matrix kernel (DKT_MLL_H2E_MINB = 1e9): every 8th episode or so scaled, the class outputscales spread so that a scaled
+    episode has classes over the bound and classes under it.  Flagged episodes equal the generic kernel on those episodes alone bit for bit, clean ones the raw split
+    kernel (no_kappa_guard) on the clean episodes alone; float64 spot checks."""
+    b, c, per, d = 2048, 5, 21, 64
+    n = c * per
+    rng = np.random.default_rng(105)
+    flagged = sorted(set(rng.choice(b, b // 8, replace=False).tolist()) - {0, b - 1})
+    clean = sorted(set(range(b)) - set(flagged))
+    e = _unit_rows_gram(b, n, d, 105, flagged, cuda)
+    y = O.one_vs_rest_targets(c, per)
+    sv = np.array([0.3, 0.45, 0.8, 1.2, 0.2])          # scaled (trace 945): classes 2, 3 over 5e3, 0, 1, 4 under;  unscaled (trace 105): all under
+    mean = np.array([0.02, -0.01, 0.0, 0.03, -0.02])
+    noise = np.full(c, 0.1)
+    cw = np.full(c, -1.0 / (c * n))
+    cw[1] = 2.0 / (c * n)
+    tr = torch.diagonal(e, dim1=1, dim2=2).sum(1).double().cpu().numpy()
+    over = 1.0 + sv[None, :] * tr[:, None] / noise[None, :] > 5e3
+    assert over[flagged].any(1).all() and not over[flagged].all(1).any() and not over[clean].any()
+    rest = [dev_t(x, cuda) for x in (y, sv, mean, noise)]
+    cwt = dev_t(cw, cuda)
+    fi, ci = torch.tensor(flagged, device=cuda), torch.tensor(clean, device=cuda)
+    gen = ops.mll(e[fi].contiguous(), *rest, want_grad=True, cls_weight=cwt, force_generic=True)
+    for minb in (None, "1000000000"):                  # wave per episode (the default at 2048 episodes), wave per matrix
+        if minb is None:
+            monkeypatch.delenv("DKT_MLL_H2E_MINB", raising=False)
+        else:
+            monkeypatch.setenv("DKT_MLL_H2E_MINB", minb)
+        _on_product_library()
+        o = ops.mll(e, *rest, want_grad=True, cls_weight=cwt)
+        torch.cuda.synchronize()
+        assert int(o["info"].abs().max().item()) == 0 and float(o["jitter"].abs().max().item()) == 0.0
+        assert torch.equal(o["w"], o["w"].transpose(1, 2))
+        _assert_units_equal(o, gen, fi)
+        monkeypatch.setenv("DKT_MLL_H2E_MINB", "1" if minb is None else minb)       # the clean sub-batch (1792 episodes) through the same kernel, unguarded
+        raw = ops.mll(e[ci].contiguous(), *rest, want_grad=True, cls_weight=cwt, no_kappa_guard=True)
+        _assert_units_equal(o, raw, ci)
+        for i in sorted({0, b - 1, flagged[0], flagged[-1], clean[1], clean[len(clean) // 2]}):
+            _mll_vs_float64(o, e, y, sv, mean, noise, cw, i)
+
+
+def test_mll_per_class_base_matrices_condition_guard_fixup(cuda):
+    """DKT_MLL_E_PER_CLASS through the f16-split kernel (one wave per (episode, class) matrix) and its fix-up, where one unit is ONE matrix: single matrices scaled over
+    the bound 5e3 are redone by the generic kernel -- bitwise the generic kernel on those episodes alone --, every other matrix, the unflagged classes of a flagged episode
+    included, stays bitwise the raw split kernel's output; float64 checks of flagged and clean matrices."""
+    b, c, n, d = 64, 5, 105, 64
+    units = [(0, 2), (5, 0), (5, 3), (17, 4), (33, 1), (40, 0), (63, 2), (63, 4)]
+    e = _unit_rows_gram(b, n, d, 64, units, cuda, per_class=c)
+    y = O.one_vs_rest_targets(c, n // c)
+    sv = np.array([0.6, 0.8, 1.0, 1.2, 0.7])             # scaled (trace 945): every class over 5e3;  unscaled (trace 105): every class under
+    mean = np.array([0.02, -0.01, 0.0, 0.03, -0.02])
+    noise = np.full(c, 0.1)
+    cw = np.full(c, -1.0 / (c * n))
+    flag = torch.zeros(b, c, dtype=torch.bool, device=cuda)
+    for u in units:
+        flag[u] = True
+    tr = torch.diagonal(e, dim1=2, dim2=3).sum(2).double()
+    over = 1.0 + torch.tensor(sv, device=cuda).view(1, c) * tr / 0.1 > 5e3
+    assert torch.equal(over, flag)
+    rest = [dev_t(x, cuda) for x in (y, sv, mean, noise)]
+    cwt = dev_t(cw, cuda)
+    _on_product_library()
+    o = ops.mll(e, *rest, want_grad=True, cls_weight=cwt)
+    raw = ops.mll(e, *rest, want_grad=True, cls_weight=cwt, no_kappa_guard=True)
+    torch.cuda.synchronize()
+    assert o["w"].shape == (b, c, n, n) and int(o["info"].abs().max().item()) == 0 and float(o["jitter"].abs().max().item()) == 0.0
+    assert torch.equal(o["w"], o["w"].transpose(2, 3))
+    eps = sorted({u[0] for u in units})
+    gen = ops.mll(e[eps].contiguous(), *rest, want_grad=True, cls_weight=cwt, force_generic=True)
+    for j, i in enumerate(eps):
+        for k in range(c):
+            _assert_units_equal(o, gen if flag[i, k] else raw, (i, k), (j, k) if flag[i, k] else (i, k))
+    _assert_units_equal(o, raw, ~flag, ~flag)
+    assert not torch.equal(o["w"][flag], raw["w"][flag])                 # (the fix-up did replace the flagged matrices)
+    for i in (0, 5, 17, 31, 63):
+        _mll_vs_float64(o, e, y, sv, mean, noise, cw, i, per_class=True)
+
+
 @pytest.mark.parametrize("b,n,d", [(72, 190, 512), (72, 320, 512), (72, 420, 512), (72, 431, 36), (72, 290, 64), (72, 447, 100), (136, 190, 512), (130, 250, 128)])
 def test_gram_large_n_kernel_twins(cuda, b, n, d):
     """N > 128, unit rows, a batch that takes the round-4 kernels (episode-resident Gram for N <= 432; Gram backward in 128-row blocks for N > 256): against the
@@ -1904,8 +2115,8 @@ def test_bench_batch_cfg0_regression_head_vs_oracle(cuda):
 
 
 def test_bench_batch_cfg4_full_chunk_and_ragged_tail(cuda):
-    """BASELINE.json configs[4] at the batch the bench runs: one FULL 1024-episode chunk of the tile-array marginal likelihood plus a
-    ragged second chunk of 6 (N = 420, C = 20, D = 512), default dispatch: residual K alpha = y - m on the first / last episodes of the
+    """BASELINE.json configs[4] at the batch the bench runs: one FULL 1024-episode chunk of the band-reduction marginal likelihood (the default from
+    12 classes and 192 episodes) plus a ragged second chunk of 6 (N = 420, C = 20, D = 512), default dispatch: residual K alpha = y - m on the first / last episodes of the
     full chunk and on the tail, symmetric W, oracle spot checks in both chunks, bitwise determinism of a second call."""
     b, d, c, per = 1030, 512, 20, 21
     n = c * per
@@ -1936,13 +2147,48 @@ def test_bench_batch_cfg4_full_chunk_and_ragged_tail(cuda):
         assert rel_l2(z.grad[i].cpu().numpy(), ref["dz"]) < GRAD_RTOL
 
 
+def test_bench_batch_cfg4_n320(cuda):
+    """bench.py's cfg4_n320 workload on its default path: N = 320 (C = 20, 16 per class), D = 512, 1030 episodes -- the band reduction, one full 1024-episode chunk
+    plus a ragged chunk of 6 (the oracle's outputscales keep every episode under the band's condition guard: no fix-up) --: residual K alpha = y - m in both chunks,
+    bitwise determinism of a second call, oracle spot checks of logp and dZ in the full chunk, at its last episode and in the tail."""
+    b, d, c, per = 1030, 512, 20, 16
+    n = c * per
+    gen = torch.Generator(device=cuda).manual_seed(320)
+    zr = torch.randn(b, n, d, generator=gen, device=cuda)
+    zr = (zr - zr.mean(1, keepdim=True)) / torch.sqrt(zr.var(1, unbiased=False, keepdim=True) + 1e-5)
+    z = torch.nn.functional.normalize(zr, dim=2).contiguous().requires_grad_(True)
+    del zr
+    y = dev_t(O.one_vs_rest_targets(c, per), cuda)
+    hyp = O.perturbed_hypers(c, 9)
+    assert 1.0 + hyp.outputscale.max() * n / hyp.noise.min() < 2e4
+    sv, mean, noise = dev_t(hyp.outputscale, cuda), dev_t(hyp.mean, cuda), dev_t(hyp.noise, cuda)
+    cw = torch.full((c,), -1.0 / (c * n), device=cuda)
+    _on_product_library()
+    obj, logp, alpha, info, jit, e = ops.episode_loss_linear(z, y, sv, mean, noise, cw, unit_rows=True)
+    obj.sum().backward()
+    assert int(info.abs().max().item()) == 0 and torch.isfinite(logp).all() and float(jit.abs().max()) == 0.0
+    for lo, hi in ((0, 24), (1000, 1030)):
+        k = sv.view(1, c, 1, 1) * e[lo:hi].unsqueeze(1) + noise.view(1, c, 1, 1) * torch.eye(n, device=cuda)
+        r = torch.matmul(k.double(), alpha[lo:hi].double().unsqueeze(-1)).squeeze(-1) - (y.double().unsqueeze(0) - mean.double().view(1, c, 1))
+        assert r.abs().max().item() < 5e-4
+        del k, r
+    z2 = z.detach().clone().requires_grad_(True)
+    obj2, logp2, *_ = ops.episode_loss_linear(z2, y, sv, mean, noise, cw, unit_rows=True)
+    obj2.sum().backward()
+    assert torch.equal(logp, logp2) and torch.equal(z.grad, z2.grad)
+    for i in (3, 1023, 1029):                      # inside the full chunk, its last episode, the ragged tail
+        ref = O.train_episode(z[i].detach().cpu().numpy().astype(np.float64), c, hyp)
+        assert np.abs((logp[i].cpu().numpy() - ref["logp"]) / ref["logp"]).max() < MLL_RTOL
+        assert rel_l2(z.grad[i].cpu().numpy(), ref["dz"]) < GRAD_RTOL
+
+
 @pytest.mark.parametrize("n_way,per", [(20, 21), (20, 16)], ids=["cfg4_n420", "cfg4_n320"])
 def test_full_size_properties_cfg4(cuda, n_way, per):
     """BASELINE.json configs[4] (20-way, ResNet18 features D = 512; N = 420 as train_loop builds it and the 320 x 320 Gram the
-    config quotes) at a full chunk of the blocked large-N path plus a ragged second chunk: residual K alpha = y - m for every
+    config quotes) at 132 episodes -- below the band reduction's 192, so the default dispatch takes the tile-array path (one pass): residual K alpha = y - m for every
     episode and class, symmetric unit-diagonal Gram, bitwise determinism, linearity of the backward, oracle spot checks --
     through the asynchronous (no host read-back) call."""
-    b, d, c = 132, 512, n_way                      # 128 = one workspace chunk, + 4
+    b, d, c = 132, 512, n_way
     n = c * per
     gen = torch.Generator(device="cpu").manual_seed(4321)
     zr = torch.randn(b, n, d, generator=gen)
@@ -1968,7 +2214,7 @@ def test_full_size_properties_cfg4(cuda, n_way, per):
     obj2, logp2, *_ = ops.episode_loss_linear(z2, y, sv, mean, noise, cw, unit_rows=True)
     obj2.sum().backward()
     assert torch.equal(logp, logp2) and torch.equal(z.grad, z2.grad)
-    for i in (0, 127, 131):                        # first chunk, its last episode, the ragged tail
+    for i in (0, 127, 131):
         ref = O.train_episode(z[i].detach().cpu().numpy().astype(np.float64), c, hyp)
         assert np.abs((logp[i].cpu().numpy() - ref["logp"]) / ref["logp"]).max() < MLL_RTOL
         assert rel_l2(z.grad[i].cpu().numpy(), ref["dz"]) < GRAD_RTOL
