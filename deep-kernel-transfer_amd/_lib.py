@@ -3,8 +3,11 @@
 There is NO CPU fallback: every entry point of `ops` goes through this library, and `load()`
 raises if the shared object is missing or a symbol of the header is absent.
 
-Three in-tree shared objects, all hipcc --offload-arch=gfx950:
+Four in-tree shared objects, all hipcc --offload-arch=gfx950:
   libdkt_hip.so    the PRODUCT: the default kernel of every call, no measurement switch, no variant instantiation;
+  libdkt_x16.so    also product code: the six front-end calls for 16-bit (bf16 / f16) trunk features of a mixed-precision backbone (include/dkt_abi_x16.h,
+                   csrc/dkt_frontend_x16.hip: the fp32 front-end templates instantiated for 16-bit X / dX).  A library of its own so that the product
+                   library's ABI and kernel list stay as they are;
   libdkt_twins.so  the same sources with -DDKT_TWINS: every pipeline variant, legacy pipeline and validation twin the defaults were chosen from, selected
                    by the environment switches of DESIGN.md's appendix.  Same ABI.  Loaded by the tests / A-B tools only (DKT_TWINS=1 + a variant switch);
   libdkt_diag.so   measurement-only kernels (stream ceilings, co-residency spinners, the round-1 register-sweep kernel).
@@ -28,7 +31,10 @@ SOURCES = ["dkt_gram.hip", "dkt_gram_ep.hip", "dkt_gram_big.hip", "dkt_gram_smal
 DIAG_SOURCES = ["dkt_diag.hip", "dkt_mll_reg_twin.hip"]
 DIAG_LIB_PATH = os.path.join(_HERE, "libdkt_diag.so")
 TWINS_LIB_PATH = os.path.join(_HERE, "libdkt_twins.so")
-HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(INCLUDE, "dkt_abi.h")]
+# 16-bit trunk features (mixed-precision backbones): product code, a library of its own (include/dkt_abi_x16.h)
+X16_SOURCES = ["dkt_frontend_x16.hip"]
+X16_LIB_PATH = os.path.join(_HERE, "libdkt_x16.so")
+HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(INCLUDE, "dkt_abi.h"), os.path.join(INCLUDE, "dkt_abi_x16.h")]
 OBJ_DIR = os.path.join(_HERE, "build")
 
 _c_p = ctypes.c_void_p
@@ -73,6 +79,21 @@ SIGNATURES = {
     "dkt_lowrank_bwd_f32": (_c_i, [_c_p] * 6 + [_c_i, _c_i, _c_i, _c_i, _c_p]),
     "dkt_smk_f32": (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_p]),
     "dkt_smk_bwd_f32": (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p]),
+}
+
+# libdkt_x16.so (include/dkt_abi_x16.h; tests check that this lists every function of the header): each front-end call of SIGNATURES with `int xdtype` after X
+X_BF16 = 1
+X_F16 = 2
+X16_SIGNATURES = {
+    "dkt_x16_abi_version": (_c_i, []),
+    "dkt_x16_reload_env": (None, []),
+    "dkt_bn_stats_x16": (_c_i, [_c_p, _c_i, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p]),
+    "dkt_gram_bn_x16": (_c_i, [_c_p, _c_i, _c_p, _c_p, ctypes.c_long, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p]),
+    "dkt_gram_bn_train_x16": (_c_i, [_c_p, _c_i, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p]),
+    "dkt_gram_bn_bwd_x16": (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_p, _c_p, ctypes.c_long, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                   _c_i, _c_i, _c_i, _c_p]),
+    "dkt_affine_normalize_x16": (_c_i, [_c_p, _c_i, _c_p, _c_p, ctypes.c_long, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p]),
+    "dkt_normalize_bn_bwd_x16": (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_p, ctypes.c_long, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p]),
 }
 
 _lock = threading.Lock()
@@ -220,7 +241,7 @@ def _compile_link(sources, target, replace=None, verbose=False, twins: bool = Fa
                     keep.update(json.load(fh))
         for f in os.listdir(OBJ_DIR):
             base = f[:-len(".res.json")] if f.endswith(".res.json") else f
-            if base.endswith(".o") and base not in keep and any(base.startswith(src + ".") for src in SOURCES + DIAG_SOURCES):
+            if base.endswith(".o") and base not in keep and any(base.startswith(src + ".") for src in SOURCES + DIAG_SOURCES + X16_SOURCES):
                 try:
                     os.remove(os.path.join(OBJ_DIR, f))
                 except OSError:
@@ -229,15 +250,34 @@ def _compile_link(sources, target, replace=None, verbose=False, twins: bool = Fa
 
 
 def build(force: bool = False, verbose: bool = False, out: str = None, replace: dict = None) -> str:
-    """hipcc --offload-arch=gfx950 -> deep-kernel-transfer_amd/libdkt_hip.so (in-tree).
-    Cross-compiles without a GPU.  `out` / `replace` ({source name: other path}) build a variant library for A/B runs."""
+    """hipcc --offload-arch=gfx950 -> deep-kernel-transfer_amd/libdkt_hip.so (in-tree), and libdkt_x16.so brought up to date as well (its own stamp:
+    it is built even when the product library is current).  Cross-compiles without a GPU.  `out` / `replace` ({source name: other path}) build a
+    variant library for A/B runs (the product library only)."""
     if out is None and not force and not needs_build():
+        build_x16(verbose)
         return LIB_PATH
     if force and os.path.isdir(OBJ_DIR):
         for f in os.listdir(OBJ_DIR):
             if f.endswith(".o"):
                 os.remove(os.path.join(OBJ_DIR, f))
-    return _compile_link(SOURCES, out or LIB_PATH, replace, verbose)
+    path = _compile_link(SOURCES, out or LIB_PATH, replace, verbose)
+    if out is None:
+        build_x16(verbose)
+    return path
+
+
+def x16_needs_build() -> bool:
+    if not os.path.exists(X16_LIB_PATH) or not os.path.exists(X16_LIB_PATH + ".stamp"):
+        return True
+    with open(X16_LIB_PATH + ".stamp") as fh:
+        return fh.read() != _stamp(X16_SOURCES)
+
+
+def build_x16(verbose: bool = False) -> str:
+    """The 16-bit front-end library libdkt_x16.so (product code: the spill check applies, budget 0)."""
+    if not x16_needs_build():
+        return X16_LIB_PATH
+    return _compile_link(X16_SOURCES, X16_LIB_PATH, None, verbose)
 
 
 def build_twins(verbose: bool = False) -> str:
@@ -437,6 +477,46 @@ def load_twins() -> ctypes.CDLL:
         build_twins()
         _twins_checked = True
     return load(TWINS_LIB_PATH)
+
+
+_x16_checked = False
+
+
+def x16_abi_version_of_header() -> int:
+    """DKT_X16_ABI_VERSION as include/dkt_abi_x16.h declares it."""
+    import re
+    with open(os.path.join(INCLUDE, "dkt_abi_x16.h")) as fh:
+        return int(re.search(r"#define\s+DKT_X16_ABI_VERSION\s+(\d+)", fh.read()).group(1))
+
+
+def load_x16() -> ctypes.CDLL:
+    """dlopen libdkt_x16.so and bind every function of include/dkt_abi_x16.h; built on first use where the sources are present (the staleness check runs
+    once per process).  Raises (never falls back) when it cannot be built or loaded."""
+    global _x16_checked
+    if not _x16_checked:
+        if os.path.isdir(CSRC):
+            build_x16()
+        _x16_checked = True
+    path = X16_LIB_PATH
+    with _lock:
+        lib = _libs.get(path)
+        if lib is not None:
+            return lib
+        if not os.path.exists(path):
+            raise RuntimeError("%s is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` -- 16-bit trunk features have no fallback." % path)
+        lib = ctypes.CDLL(path)
+        for name, (res, args) in X16_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise RuntimeError("%s lacks symbol %s declared in include/dkt_abi_x16.h" % (os.path.basename(path), name)) from e
+            fn.restype = res
+            fn.argtypes = args
+        want, got = x16_abi_version_of_header(), int(lib.dkt_x16_abi_version())
+        if got != want:
+            raise RuntimeError("%s implements DKT_X16_ABI_VERSION %d, include/dkt_abi_x16.h declares %d: rebuild" % (path, got, want))
+        _libs[path] = lib
+        return lib
 
 
 def load_diag() -> ctypes.CDLL:

@@ -6,6 +6,10 @@ kernel_type: 'bncossim' (default), 'cossim', 'linear', 'rbf', 'matern', 'poli1',
 """
 kernel_type = 'bncossim'
 
+# mixed-precision backbone of the models a process builds when their constructor is not told (DKT / DKTRegression amp=None): None (fp32) or 'bf16'.
+# The drivers' `--amp` flag sets it (io_utils.parse_args), as `--kernel_type` feeds kernel_type.
+amp = None
+
 save_dir = './save/'                     # checkpoints: <save_dir>checkpoints/<dataset>/<model>_<method>[_aug]_<n>way_<k>shot
 
 # file-list roots of the image datasets (only used when such a tree and torchvision are present; `--dataset synthetic` needs none)

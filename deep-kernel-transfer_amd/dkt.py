@@ -17,6 +17,8 @@ no per-class host syncs (DKT.py:151-154, 180, 190).
 """
 from __future__ import annotations
 
+import contextlib
+import functools
 from time import gmtime, strftime
 
 import os
@@ -59,6 +61,39 @@ class _MllView(nn.Module):
     def forward(self, z, targets):
         loss, _ = self._owner._episode_loss(z, targets)
         return -loss
+
+
+AMP_MODES = (None, "bf16")
+
+
+def amp_mode(amp):
+    """amp=None | "none" | "bf16" -> None | "bf16" (the only mixed-precision mode the models offer; f16 features from a caller's own
+    torch.autocast block are accepted as they come).  None / "none" = fp32."""
+    amp = None if amp in (None, "none") else amp
+    if amp not in AMP_MODES:
+        raise ValueError("amp must be None or 'bf16', got %r" % (amp,))
+    return amp
+
+
+def backbone_autocast(amp):
+    """The backbone's autocast region: bf16 under amp="bf16" (cache_enabled=False: the step may be captured into a hipGraph); otherwise nothing --
+    a caller's own torch.autocast block then applies as it is."""
+    if amp == "bf16":
+        return torch.autocast("cuda", dtype=torch.bfloat16, cache_enabled=False)
+    return contextlib.nullcontext()
+
+
+def gp_head(fn):
+    """Runs a method of the GP head with autocast disabled (amp="bf16" and a caller's outer torch.autocast alike): its tensors stay fp32."""
+    @functools.wraps(fn)
+    def wrapped(*args, **kwargs):
+        with torch.autocast("cuda", enabled=False):
+            return fn(*args, **kwargs)
+    return wrapped
+
+
+def _autocast_active(amp) -> bool:
+    return amp is not None or torch.is_autocast_enabled("cuda")
 
 
 class _FusableBatchNorm1d(nn.BatchNorm1d):
@@ -136,9 +171,13 @@ class _GraphedTrainStep:
 
 
 class DKT(MetaTemplate):
-    def __init__(self, model_func, n_way, n_support, kernel_type=None):
+    def __init__(self, model_func, n_way, n_support, kernel_type=None, amp=None):
         super(DKT, self).__init__(model_func, n_way, n_support)
         self.kernel_type = configs.kernel_type if kernel_type is None else kernel_type
+        # mixed-precision backbone (opt-in): "bf16" runs the backbone under torch.autocast up to, not including, bn_out; the GP head stays fp32.
+        # The fused front end takes the 16-bit trunk features as they are (libdkt_x16.so); every other route converts them once with .float().
+        # amp=None takes configs.amp (the drivers' --amp; None by default), "none" is fp32 whatever configs says
+        self.amp = configs.amp if amp is None else amp
         self.leghtscale_list = None
         self.noise_list = None
         self.outputscale_list = None
@@ -159,6 +198,14 @@ class DKT(MetaTemplate):
         self._target_cache = {}
         self._grad_bucket = None
         self._last = {}
+
+    @property
+    def amp(self):
+        return self._amp
+
+    @amp.setter
+    def amp(self, value):
+        object.__setattr__(self, "_amp", amp_mode(value))
 
     # ------------------------------------------------------------------ construction
     def init_summary(self):
@@ -219,9 +266,20 @@ class DKT(MetaTemplate):
                                "(train_n_way must equal test_n_way for DKT)" % (self.model.n_models, n_way))
 
     def _embed(self, x):
-        z = self.feature_extractor.forward(x)
-        if self.normalize:
-            z = F.normalize(z, p=2, dim=1)
+        if not _autocast_active(self.amp):
+            z = self.feature_extractor.forward(x)
+            if self.normalize:
+                z = F.normalize(z, p=2, dim=1)
+            return z
+        # mixed precision: the backbone under autocast, then ONE conversion to fp32 at the head boundary and bn_out / F.normalize in fp32
+        z = self._trunk_features(x)
+        bn = getattr(self.feature_extractor.trunk, "bn_out", None)
+        with torch.autocast("cuda", enabled=False):
+            z = z.float()
+            if bn is not None:
+                z = bn(z)
+            if self.normalize:
+                z = F.normalize(z, p=2, dim=1)
         return z
 
     def _hypers(self):
@@ -232,19 +290,21 @@ class DKT(MetaTemplate):
     def _trunk_features(self, x):
         """Backbone output BEFORE bn_out (the module the reference appends to the trunk at DKT.py:48)."""
         bn = getattr(self.feature_extractor.trunk, "bn_out", None)
-        if bn is None:
-            return self.feature_extractor.forward(x)
-        bn.bypass = True
-        try:
-            return self.feature_extractor.forward(x)
-        finally:
-            bn.bypass = False
+        with backbone_autocast(self.amp):
+            if bn is None:
+                return self.feature_extractor.forward(x)
+            bn.bypass = True
+            try:
+                return self.feature_extractor.forward(x)
+            finally:
+                bn.bypass = False
 
     def _fused_front_end(self, n, d):
         # (n <= 128: the episode-resident kernels of dkt_frontend.hip; up to 448 rows: the streaming kernels of dkt_frontend_big.hip in front of the large-N Gram kernels)
         return (self.kernel_type in ("bncossim", "cossim") and n <= 448 and d % 4 == 0
                 and os.environ.get("DKT_FUSED_FRONTEND", "1") != "0")
 
+    @gp_head
     def _episode_loss_from_trunk(self, x_feat, y, want_z=True):
         """Training loss of ONE episode from the trunk output x_feat:[N,D] (or the mean over a meta-batch [B,N,D]); bn_out runs
         in train mode (batch statistics of EACH episode, running estimates updated exactly as nn.BatchNorm1d would after seeing
@@ -289,6 +349,7 @@ class DKT(MetaTemplate):
         aux = dict(logp=logp, alpha=alpha, info=info, jitter=jit, e=None if e is None else e.detach())
         return obj.mean(), aux, z_train
 
+    @gp_head
     def _episode_loss(self, z, y):
         """loss = -(1/C) sum_c logp_c / N for ONE episode z:[N,D] (or a batch [B,N,D] -> mean over B)."""
         zb = z if z.dim() == 3 else z.unsqueeze(0)
@@ -329,6 +390,7 @@ class DKT(MetaTemplate):
         aux = dict(logp=logp, alpha=alpha, info=info, jitter=jit, e=None if e is None else e.detach())
         return obj.mean(), aux
 
+    @gp_head
     def _posterior(self, z_cond, y, z_star, e_cond=None):
         """Mean cache on the conditioning set, posterior means [C,M] and labels [M] at z_star."""
         sv, mean, noise = self._hypers()
@@ -387,6 +449,11 @@ class DKT(MetaTemplate):
         d = x_feat.shape[1]
         if x_feat.dim() != 2 or not self._fused_front_end(ns + nq, d):
             return None
+        with torch.autocast("cuda", enabled=False):          # the GP head: fp32 (16-bit trunk features go to the *_x16 front-end kernels as they are)
+            return self._posterior_fused_eval_head(x_feat, ns, nq, y, bn)
+
+    def _posterior_fused_eval_head(self, x_feat, ns, nq, y, bn):
+        d = x_feat.shape[1]
         if bn is not None:
             a = bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps) if bn.affine else torch.rsqrt(bn.running_var + bn.eps)
             s = (bn.bias.detach() if bn.affine else 0.0) - bn.running_mean * a
@@ -412,12 +479,19 @@ class DKT(MetaTemplate):
         # ONE backbone pass over the nb * N images of the step (meta-batch: the backbone's own BatchNorm2d layers then see
         # all of them as one batch, as any mini-batch training does; bn_out and the GPs stay per episode)
         x_feat = self._trunk_features(x_all)
+        with torch.autocast("cuda", enabled=False):          # the GP head: fp32 (see _train_forward_head)
+            return self._train_forward_head(x_feat, y_targets, nb, n_ep, want_z)
+
+    def _train_forward_head(self, x_feat, y_targets, nb, n_ep, want_z):
+        """The GP side of a training step from the trunk features: the fused front end takes them as they are (fp32, or 16-bit from a backbone under
+        autocast: the *_x16 kernels); every other route converts them once to fp32 in front of bn_out ("accepted, not native")."""
         fused = x_feat.dim() == 2 and self._fused_front_end(n_ep, x_feat.shape[1])
         if fused:
             if nb > 1:
                 x_feat = x_feat.view(nb, n_ep, -1)
             loss, aux, z_train = self._episode_loss_from_trunk(x_feat, y_targets, want_z=want_z)
             return loss, aux, z_train, True
+        x_feat = x_feat.float()
         bn = getattr(self.feature_extractor.trunk, "bn_out", None)        # torch bn_out / F.normalize in front of the Gram kernels
         if bn is None:
             z_train = x_feat

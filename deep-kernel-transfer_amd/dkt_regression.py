@@ -18,11 +18,12 @@ import torch
 import torch.nn as nn
 
 from . import configs, ops
+from .dkt import amp_mode, backbone_autocast, gp_head
 from .gp import ExactGPHypers, RBF_KINDS, SPECTRAL_KINDS
 
 
 class DKT(nn.Module):
-    def __init__(self, backbone, kernel_type=None, batch_fn=None, num_mixtures=4, ard_num_dims=2916):
+    def __init__(self, backbone, kernel_type=None, batch_fn=None, num_mixtures=4, ard_num_dims=2916, amp=None):
         super(DKT, self).__init__()
         self.kernel_type = configs.kernel_type if kernel_type is None else kernel_type
         if self.kernel_type not in RBF_KINDS + SPECTRAL_KINDS:
@@ -34,6 +35,8 @@ class DKT(nn.Module):
         self.batch_fn = batch_fn
         self.jitter0 = 1e-6
         self.max_tries = 3
+        # "bf16": the backbone under torch.autocast, the features converted once to fp32 for the GP (RBF / spectral: fp32 kernels); None: configs.amp
+        self.amp = configs.amp if amp is None else amp
         self.get_model_likelihood_mll()
 
     def get_model_likelihood_mll(self, train_x=None, train_y=None):
@@ -53,6 +56,22 @@ class DKT(nn.Module):
     def device(self):
         return self.model.mean_constant.device
 
+    @property
+    def amp(self):
+        return self._amp
+
+    @amp.setter
+    def amp(self, value):
+        object.__setattr__(self, "_amp", amp_mode(value))
+
+    def _features(self, x):
+        """Backbone features for the GP: under amp="bf16" (or a caller's torch.autocast) the backbone runs in 16 bits and its output is converted
+        to fp32 once at the head boundary -- the RBF / spectral kernels take fp32 features ("accepted, not native")."""
+        with backbone_autocast(self.amp):
+            z = self.feature_extractor(x)
+        return z.float()
+
+    @gp_head
     def _loss(self, z, labels):
         """loss = -logp / N for one task z:[N,D] or a batch [B,N,D] with labels [N] / [B,N] (mean over B)."""
         zb = z if z.dim() == 3 else z.unsqueeze(0)
@@ -74,7 +93,7 @@ class DKT(nn.Module):
         batch, batch_labels = batch.to(self.device), batch_labels.to(self.device)
         for inputs, labels in zip(batch, batch_labels):
             optimizer.zero_grad()
-            z = self.feature_extractor(inputs)
+            z = self._features(inputs)
             loss, _ = self._loss(z, labels)
             loss.backward()
             optimizer.step()
@@ -85,6 +104,7 @@ class DKT(nn.Module):
                 print('[%d] - Loss: %.3f  MSE: %.3f noise: %.3f' % (epoch, loss.item(), mse.item(), self.model.noise.item()))
 
     @torch.no_grad()
+    @gp_head
     def predict(self, z_support, y_support, z_all, with_variance=False):
         """Condition on the support frames, posterior mean (and variance + noise) at z_all."""
         m = self.model
@@ -121,8 +141,8 @@ class DKT(nn.Module):
         self.model.eval()
         self.feature_extractor.eval()
         with torch.no_grad():
-            z_support = self.feature_extractor(x_support[n]).detach()
-            z_query = self.feature_extractor(x_all[n]).detach()
+            z_support = self._features(x_support[n]).detach()
+            z_query = self._features(x_all[n]).detach()
             mean, var = self.predict(z_support, y_support[n], z_query, with_variance=True)
             lower, upper = mean - 2.0 * var.sqrt(), mean + 2.0 * var.sqrt()   # confidence_region(), unused
         return self.mse(mean, y_all[n])

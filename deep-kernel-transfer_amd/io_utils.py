@@ -11,7 +11,20 @@ import os
 
 import numpy as np
 
+from . import configs
 from .backbone import model_dict  # noqa: F401  (re-exported like the reference's io_utils.model_dict)
+
+
+def _add_amp(parser):
+    parser.add_argument('--amp', default='none', choices=['none', 'bf16'],
+                        help='[this build] mixed-precision backbone: bf16 runs the backbone under torch.autocast, the GP head stays fp32 (default: none)')
+
+
+def _apply_amp(args):
+    """--amp becomes configs.amp, the default of every DKT / DKTRegression the process builds -- so that a driver that constructs its model
+    without passing the flag on (test_uncertainty.py) honours it too."""
+    configs.amp = None if args.amp == 'none' else args.amp
+    return args
 
 
 def parse_args(script, argv=None):
@@ -28,6 +41,7 @@ def parse_args(script, argv=None):
     parser.add_argument('--image_size', default=None, type=int, help='override the backbone-dependent image size')
     parser.add_argument('--n_episode', default=None, type=int, help='episodes per epoch (train: 100) / per test run (600)')
     parser.add_argument('--meta_batch', default=1, type=int, help='[train, this build] episodes per Adam step through the batched hot path (1 = the reference: one step per episode)')
+    _add_amp(parser)
     if script == 'train':
         parser.add_argument('--num_classes', default=200, type=int, help='(baseline only; kept for CLI compatibility)')
         parser.add_argument('--save_freq', default=50, type=int, help='Save frequency')
@@ -42,7 +56,7 @@ def parse_args(script, argv=None):
         parser.add_argument('--repeat', default=5, type=int, help='Repeat the test N times with different seeds')
     else:
         raise ValueError('Unknown script')
-    return parser.parse_args(argv)
+    return _apply_amp(parser.parse_args(argv))
 
 
 def parse_args_regression(script, argv=None):
@@ -55,6 +69,7 @@ def parse_args_regression(script, argv=None):
     parser.add_argument('--method', default='DKT', help='DKT (the feature-transfer baseline is out of scope)')
     parser.add_argument('--dataset', default='synthetic', help='synthetic / QMUL')
     parser.add_argument('--spectral', action='store_true', help='Use a spectral covariance kernel function')
+    _add_amp(parser)
     if script == 'train_regression':
         parser.add_argument('--start_epoch', default=0, type=int, help='Starting epoch')
         parser.add_argument('--stop_epoch', default=100, type=int, help='Stopping epoch')
@@ -64,7 +79,7 @@ def parse_args_regression(script, argv=None):
         parser.add_argument('--n_test_epochs', default=10, type=int, help='How many test people?')
     else:
         raise ValueError('Unknown script')
-    return parser.parse_args(argv)
+    return _apply_amp(parser.parse_args(argv))
 
 
 def get_assigned_file(checkpoint_dir, num):

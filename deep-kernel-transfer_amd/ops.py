@@ -1,7 +1,9 @@
 """Torch-facing wrappers over the C ABI (include/dkt_abi.h): raw device pointers + the current HIP
 stream go down, nothing else.  PyTorch only owns the memory and the stream.
 
-Every function REQUIRES float32 CUDA (ROCm) tensors and raises otherwise -- there is no CPU path.
+Every function REQUIRES float32 CUDA (ROCm) tensors and raises otherwise -- there is no CPU path.  The one exception is the trunk output X of
+the front-end calls (bn_stats, gram_bn, gram_bn_train, gram_bn_bwd, affine_normalize, normalize_bn_bwd, episode_loss_bn): bfloat16 / float16 X
+(a backbone under torch.autocast) goes to the 16-bit kernels of libdkt_x16.so (include/dkt_abi_x16.h), with dX in X's dtype; never an fp32 copy.
 
 Autograd surface
   episode_loss_linear(z, y, sv, mean, noise, cls_weight) -> obj[B]   (fused: gram -> mll -> gram_bwd)
@@ -60,6 +62,20 @@ def _req(t: torch.Tensor, name: str, ndim: Optional[int] = None) -> torch.Tensor
     if ndim is not None and t.dim() != ndim:
         raise RuntimeError("dkt_amd.ops: `%s` must have %d dims, got %s" % (name, ndim, tuple(t.shape)))
     return t.contiguous()
+
+
+_X16_DTYPES = {torch.bfloat16: _lib.X_BF16, torch.float16: _lib.X_F16}
+
+
+def _req_x(t: torch.Tensor, name: str, ndim: Optional[int] = None) -> torch.Tensor:
+    """The trunk output of the front-end calls: float32 (the product library), bfloat16 or float16 (libdkt_x16.so)."""
+    if isinstance(t, torch.Tensor) and t.dtype in _X16_DTYPES:
+        if not t.is_cuda:
+            raise RuntimeError("dkt_amd.ops: `%s` must be a CUDA/ROCm tensor -- the DKT hot path is HIP-only (no CPU fallback)" % name)
+        if ndim is not None and t.dim() != ndim:
+            raise RuntimeError("dkt_amd.ops: `%s` must have %d dims, got %s" % (name, ndim, tuple(t.shape)))
+        return t.contiguous()
+    return _req(t, name, ndim)
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -135,7 +151,7 @@ def _sync_env(lib, names=None) -> None:
     if seen is None or any(os.environ.get(k) != seen[k] for k in (names or _ENV_SWITCHES)):
         snap = {k: os.environ.get(k) for k in _ENV_SWITCHES}
         if seen is not None or any(v is not None for v in snap.values()):
-            lib.dkt_reload_env()
+            (lib.dkt_x16_reload_env if lib._name == _lib.X16_LIB_PATH else lib.dkt_reload_env)()
         _env_seen[id(lib)] = snap
 
 
@@ -155,6 +171,21 @@ def _lib_now(want_twin: bool = False):
         lib = _lib.load()
     _sync_env(lib)
     return lib
+
+
+def _front_end(stem: str, x: torch.Tensor, args: list, xpos: int) -> None:
+    """Launch a front-end call on X = args[xpos]: dkt_<stem>_f32 of the product library (or its twins build) for fp32 X, as always; dkt_<stem>_x16 of
+    libdkt_x16.so for bfloat16 / float16 X, with its `xdtype` inserted right after X (there is no twin of those: DKT_TWINS does not apply)."""
+    xdt = _X16_DTYPES.get(x.dtype)
+    if xdt is None:
+        name, lib = "dkt_%s_f32" % stem, _lib_now()
+    else:
+        name, lib = "dkt_%s_x16" % stem, _lib.load_x16()
+        _sync_env(lib, _PRODUCT_SWITCHES)
+        args = args[:xpos + 1] + [xdt] + args[xpos + 1:]
+    with _timed(name):
+        st = getattr(lib, name)(*args)
+    _lib.check(st, name)
 
 
 def gram(a: torch.Tensor, bm: Optional[torch.Tensor] = None, kind: int = KERNEL_LINEAR,
@@ -844,19 +875,16 @@ class _EpisodeLossLowRankFn(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------------
 def bn_stats(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float = 1e-5) -> dict:
     """Train-mode BatchNorm1d statistics per episode: x:[B,N,D] -> mean, rstd, a, s, var_unbiased (each [B,D]);
-    y = a x + s is bn_out(x)."""
-    x = _req(x, "x", 3)
+    y = a x + s is bn_out(x).  x: float32, bfloat16 or float16 (the statistics are fp32 either way)."""
+    x = _req_x(x, "x", 3)
     b_, n, d = x.shape
     if d % 4:
         raise RuntimeError("bn_stats: D must be a multiple of 4")
     gamma = None if gamma is None else _req(gamma.reshape(-1), "gamma", 1)
     beta = None if beta is None else _req(beta.reshape(-1), "beta", 1)
     out = {k: torch.empty((b_, d), device=x.device, dtype=torch.float32) for k in ("mean", "rstd", "a", "s", "var_unbiased")}
-    lib = _lib_now()
-    with _timed("dkt_bn_stats_f32"):
-        st = lib.dkt_bn_stats_f32(_p(x), _p(gamma), _p(beta), float(eps), _p(out["mean"]), _p(out["rstd"]), _p(out["a"]),
-                                  _p(out["s"]), _p(out["var_unbiased"]), b_, n, d, _stream())
-    _lib.check(st, "dkt_bn_stats_f32")
+    _front_end("bn_stats", x, [_p(x), _p(gamma), _p(beta), float(eps), _p(out["mean"]), _p(out["rstd"]), _p(out["a"]),
+                               _p(out["s"]), _p(out["var_unbiased"]), b_, n, d, _stream()], 0)
     return out
 
 
@@ -871,8 +899,8 @@ def _ab_stride(a: torch.Tensor, s: torch.Tensor, b_: int, d: int) -> int:
 
 
 def gram_bn(x: torch.Tensor, a: torch.Tensor, s: torch.Tensor):
-    """E[b] = Zn Zn^T with Zn = normalize(a x + s) (never materialised); returns (E [B,N,N], rnorm [B,N])."""
-    x = _req(x, "x", 3)
+    """E[b] = Zn Zn^T with Zn = normalize(a x + s) (never materialised); returns (E [B,N,N], rnorm [B,N]).  x: float32, bfloat16 or float16."""
+    x = _req_x(x, "x", 3)
     b_, n, d = x.shape
     if n > 128 or d % 4:
         raise RuntimeError("gram_bn: needs N <= 128 and D %% 4 == 0 (got N=%d, D=%d)" % (n, d))
@@ -881,17 +909,14 @@ def gram_bn(x: torch.Tensor, a: torch.Tensor, s: torch.Tensor):
     stride = _ab_stride(a, s, b_, d)
     e = torch.empty((b_, n, n), device=x.device, dtype=torch.float32)
     rnorm = torch.empty((b_, n), device=x.device, dtype=torch.float32)
-    lib = _lib_now()
-    with _timed("dkt_gram_bn_f32"):
-        st = lib.dkt_gram_bn_f32(_p(x), _p(a), _p(s), stride, _p(e), _p(rnorm), b_, n, d, _stream())
-    _lib.check(st, "dkt_gram_bn_f32")
+    _front_end("gram_bn", x, [_p(x), _p(a), _p(s), stride, _p(e), _p(rnorm), b_, n, d, _stream()], 0)
     return e, rnorm
 
 
 def gram_bn_train(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float = 1e-5):
     """bn_stats + gram_bn in one pass over x (train-mode BatchNorm1d statistics taken inside the Gram kernel's staging path).
-    Returns (E [B,N,N], rnorm [B,N], stats dict as bn_stats)."""
-    x = _req(x, "x", 3)
+    Returns (E [B,N,N], rnorm [B,N], stats dict as bn_stats).  x: float32, bfloat16 or float16."""
+    x = _req_x(x, "x", 3)
     b_, n, d = x.shape
     if n > 128 or d % 4:
         raise RuntimeError("gram_bn_train: needs N <= 128 and D %% 4 == 0 (got N=%d, D=%d)" % (n, d))
@@ -900,18 +925,15 @@ def gram_bn_train(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional
     out = {k: torch.empty((b_, d), device=x.device, dtype=torch.float32) for k in ("mean", "rstd", "a", "s", "var_unbiased")}
     e = torch.empty((b_, n, n), device=x.device, dtype=torch.float32)
     rnorm = torch.empty((b_, n), device=x.device, dtype=torch.float32)
-    lib = _lib_now()
-    with _timed("dkt_gram_bn_train_f32"):
-        st = lib.dkt_gram_bn_train_f32(_p(x), _p(gamma), _p(beta), float(eps), _p(out["mean"]), _p(out["rstd"]), _p(out["a"]),
-                                       _p(out["s"]), _p(out["var_unbiased"]), _p(e), _p(rnorm), b_, n, d, _stream())
-    _lib.check(st, "dkt_gram_bn_train_f32")
+    _front_end("gram_bn_train", x, [_p(x), _p(gamma), _p(beta), float(eps), _p(out["mean"]), _p(out["rstd"]), _p(out["a"]),
+                                    _p(out["s"]), _p(out["var_unbiased"]), _p(e), _p(rnorm), b_, n, d, _stream()], 0)
     return e, rnorm, out
 
 
 def gram_bn_bwd(w, e, x, a, s, rnorm, mean=None, rstd=None, ep_scale=None):
     """Backward of gram_bn (+ train-mode batch statistics when mean/rstd are given): returns (dX, dgamma_part, dbeta_part);
-    the last two are [B,D] per-episode parts (None in eval mode)."""
-    x = _req(x, "x", 3)
+    the last two are [B,D] per-episode parts (None in eval mode).  x: float32, bfloat16 or float16; dX comes back in x's dtype."""
+    x = _req_x(x, "x", 3)
     b_, n, d = x.shape
     w = _req(w, "w", 3)
     e = _req(e, "e", 3)
@@ -928,11 +950,8 @@ def gram_bn_bwd(w, e, x, a, s, rnorm, mean=None, rstd=None, ep_scale=None):
     dx = torch.empty_like(x)
     dg = torch.empty((b_, d), device=x.device, dtype=torch.float32) if train else None
     db = torch.empty((b_, d), device=x.device, dtype=torch.float32) if train else None
-    lib = _lib_now()
-    with _timed("dkt_gram_bn_bwd_f32"):
-        st = lib.dkt_gram_bn_bwd_f32(_p(w), _p(e), _p(x), _p(a), _p(s), stride, _p(mean), _p(rstd), _p(rnorm), _p(ep_scale),
-                                     _p(dx), _p(dg), _p(db), b_, n, d, _stream())
-    _lib.check(st, "dkt_gram_bn_bwd_f32")
+    _front_end("gram_bn_bwd", x, [_p(w), _p(e), _p(x), _p(a), _p(s), stride, _p(mean), _p(rstd), _p(rnorm), _p(ep_scale),
+                                  _p(dx), _p(dg), _p(db), b_, n, d, _stream()], 2)
     return dx, dg, db
 
 
@@ -961,27 +980,24 @@ def bn_param_grads(dg: torch.Tensor, db: torch.Tensor):
 
 def affine_normalize(x: torch.Tensor, a: torch.Tensor, s: torch.Tensor):
     """Zn = y / max(|y|_2, 1e-12), y = a x + s, row by row; a, s: [D] or [B,D].  Returns (Zn [B,N,D], rnorm [B,N]) (dkt_affine_normalize_f32: the front end of
-    episodes with more than 128 rows, whose Gram kernels take unit rows as input)."""
-    x = _req(x, "x", 3)
+    episodes with more than 128 rows, whose Gram kernels take unit rows as input).  x: float32, bfloat16 or float16; Zn is float32."""
+    x = _req_x(x, "x", 3)
     b_, n, d = x.shape
     a = _req(a, "a")
     s = _req(s, "s")
     stride = _ab_stride(a, s, b_, d)
-    zn = torch.empty_like(x)
+    zn = torch.empty_like(x) if x.dtype == torch.float32 else torch.empty((b_, n, d), device=x.device, dtype=torch.float32)
     rnorm = torch.empty((b_, n), device=x.device, dtype=torch.float32)
-    lib = _lib_now()
-    with _timed("dkt_affine_normalize_f32"):
-        st = lib.dkt_affine_normalize_f32(_p(x), _p(a), _p(s), stride, _p(zn), _p(rnorm), b_, n, d, _stream())
-    _lib.check(st, "dkt_affine_normalize_f32")
+    _front_end("affine_normalize", x, [_p(x), _p(a), _p(s), stride, _p(zn), _p(rnorm), b_, n, d, _stream()], 0)
     return zn, rnorm
 
 
 def normalize_bn_bwd(dzn, zn, x, a, rnorm, mean=None, rstd=None):
     """Backward of affine_normalize (+ the train-mode batch statistics behind a, s when mean / rstd are given): (dX, dgamma_part [B,D], dbeta_part [B,D]) --
-    the parts are None without statistics (dkt_normalize_bn_bwd_f32)."""
+    the parts are None without statistics (dkt_normalize_bn_bwd_f32).  x: float32, bfloat16 or float16; dX comes back in x's dtype."""
     dzn = _req(dzn, "dzn", 3)
     zn = _req(zn, "zn", 3)
-    x = _req(x, "x", 3)
+    x = _req_x(x, "x", 3)
     b_, n, d = x.shape
     a = _req(a, "a")
     rnorm = _req(rnorm, "rnorm", 2)
@@ -994,10 +1010,8 @@ def normalize_bn_bwd(dzn, zn, x, a, rnorm, mean=None, rstd=None):
     dg = torch.empty((b_, d), device=x.device, dtype=torch.float32) if train else None
     db = torch.empty((b_, d), device=x.device, dtype=torch.float32) if train else None
     ws = torch.empty((b_, n), device=x.device, dtype=torch.float32)
-    lib = _lib_now()
-    with _timed("dkt_normalize_bn_bwd_f32"):
-        st = lib.dkt_normalize_bn_bwd_f32(_p(dzn), _p(zn), _p(x), _p(a), stride, _p(mean), _p(rstd), _p(rnorm), _p(dx), _p(dg), _p(db), _p(ws), b_, n, d, _stream())
-    _lib.check(st, "dkt_normalize_bn_bwd_f32")
+    _front_end("normalize_bn_bwd", x, [_p(dzn), _p(zn), _p(x), _p(a), stride, _p(mean), _p(rstd), _p(rnorm), _p(dx), _p(dg), _p(db), _p(ws), b_, n, d,
+                                       _stream()], 2)
     return dx, dg, db
 
 
@@ -1008,7 +1022,9 @@ class _EpisodeLossBnFn(torch.autograd.Function):
     (dkt_gram_bn_train_f32; DKT_FUSED_STATS=0: dkt_bn_stats_f32 + dkt_gram_bn_f32) -> MLL (dkt_mll_f32) ; backward dkt_gram_bn_bwd_f32.  The normalised features are
     never written to memory.  use_bn=False is the plain cossim kernel (no bn_out: affine map = identity).
     More than 128 rows (the 20-way shapes): dkt_bn_stats_f32 -> dkt_affine_normalize_f32 (Zn written once: the large-N Gram kernels take unit rows as input) ->
-    dkt_gram_f32 -> dkt_mll_f32; backward dkt_gram_bwd_f32 -> dkt_normalize_bn_bwd_f32."""
+    dkt_gram_f32 -> dkt_mll_f32; backward dkt_gram_bwd_f32 -> dkt_normalize_bn_bwd_f32.
+    X in bfloat16 / float16 (a mixed-precision backbone): the same route through the *_x16 twins of the front-end calls; the gradient of X comes back
+    in X's dtype, everything behind the front end (Zn, E, the marginal likelihood, the hyper-parameter and BatchNorm gradients) is fp32."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, use_bn, y, sv, mean, noise, cls_weight, jitter0, max_tries):
@@ -1090,7 +1106,7 @@ class _EpisodeLossBnFn(torch.autograd.Function):
 
 def episode_loss_bn(x, gamma, beta, y, sv, mean, noise, cls_weight, eps: float = 1e-5, jitter0: float = 1e-6, max_tries: int = 3,
                     use_bn: bool = True, full: bool = False):
-    """x:[B,N,D] trunk output BEFORE bn_out.  Returns (obj[B], logp, alpha, info, jitter, E (None when the episode ran in feature space: lowrank_applies), batch_mean[B,D],
+    """x:[B,N,D] trunk output BEFORE bn_out (float32, bfloat16 or float16).  Returns (obj[B], logp, alpha, info, jitter, E (None when the episode ran in feature space: lowrank_applies), batch_mean[B,D],
     batch_var_unbiased[B,D]) -- the last two feed the caller's running-statistics update -- plus, with full=True, the folded
     affine map a, s and the row scales rnorm (zn = (a x + s) rnorm: what a caller needs to re-create the normalised features)."""
     out = _EpisodeLossBnFn.apply(x, gamma, beta, eps, use_bn, y, sv, mean, noise, cls_weight, jitter0, max_tries)

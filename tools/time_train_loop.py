@@ -1,5 +1,6 @@
 """Wall time per episode of the drop-in DKT.train_loop / test_loop (level-2 context of SURVEY.md 8d: synthetic images through
-the backbone + the GP hot path, one Adam step per episode as the reference does).  Measurement tooling; prints only."""
+the backbone + the GP hot path, one Adam step per episode as the reference does).  Measurement tooling; prints only.
+--amp bf16: the backbone under torch.autocast (DKT(amp="bf16")); --amp both: each backbone without, then with it."""
 import os
 import sys
 import time
@@ -26,9 +27,11 @@ class Loader:
         return iter((self.x[i % len(self.x)], None) for i in range(self.n))
 
 
+amp_arg = sys.argv[sys.argv.index("--amp") + 1] if "--amp" in sys.argv else "none"
+amps = ("none", "bf16") if amp_arg == "both" else (amp_arg,)
 dev = torch.device("cuda", 0)
-for name, hw in (("Conv4S", 28), ("Conv4", 84), ("ResNet10", 224)):
-    m = dkt_amd.DKT(getattr(dkt_amd.backbone, name), n_way=5, n_support=5).to(dev)
+for name, hw, amp in [(n_, h_, a_) for n_, h_ in (("Conv4S", 28), ("Conv4", 84), ("ResNet10", 224)) for a_ in amps]:
+    m = dkt_amd.DKT(getattr(dkt_amd.backbone, name), n_way=5, n_support=5, amp=amp).to(dev)
     mb = int(os.environ.get("DKT_META_BATCH", "1"))          # episodes per Adam step (train.py --meta_batch)
     m.meta_batch = mb
     n_ep = (40 if name != "ResNet10" else 12) * (mb if mb > 1 else 1) // (4 if mb >= 16 else 1)
@@ -52,4 +55,4 @@ for name, hw in (("Conv4S", 28), ("Conv4", 84), ("ResNet10", 224)):
     torch.cuda.synchronize()
     dte = (time.perf_counter() - t1) / n_ep
     sys.stdout = sys.__stdout__
-    print("device_data=%s meta_batch=%d graph=%s fused_adam=%s %-9s %3dx%-3d  train_loop %.2f ms / episode (%.0f episodes/s)   test_loop %.2f ms / episode" % (os.environ.get("DKT_DEVICE_DATA", "0"), mb, os.environ.get("DKT_TRAIN_GRAPH", "0"), os.environ.get("DKT_FUSED_ADAM", "1"), name, hw, hw, 1e3 * dt, 1 / dt, 1e3 * dte), flush=True)
+    print("amp=%s device_data=%s meta_batch=%d graph=%s fused_adam=%s %-9s %3dx%-3d  train_loop %.2f ms / episode (%.0f episodes/s)   test_loop %.2f ms / episode" % (amp, os.environ.get("DKT_DEVICE_DATA", "0"), mb, os.environ.get("DKT_TRAIN_GRAPH", "0"), os.environ.get("DKT_FUSED_ADAM", "1"), name, hw, hw, 1e3 * dt, 1 / dt, 1e3 * dte), flush=True)
