@@ -8,6 +8,8 @@ Four in-tree shared objects, all hipcc --offload-arch=gfx950:
   libdkt_x16.so    also product code: the six front-end calls for 16-bit (bf16 / f16) trunk features of a mixed-precision backbone (include/dkt_abi_x16.h,
                    csrc/dkt_frontend_x16.hip: the fp32 front-end templates instantiated for 16-bit X / dX).  A library of its own so that the product
                    library's ABI and kernel list stay as they are;
+  libdkt_data.so   the episode image transform of the image-dataset loader (include/dkt_abi_data.h, csrc/dkt_augment.hip: Pillow's bilinear resize,
+                   ImageEnhance jitter, flip, ToTensor + Normalize, bit for bit).  A library of its own, like libdkt_x16.so;
   libdkt_twins.so  the same sources with -DDKT_TWINS: every pipeline variant, legacy pipeline and validation twin the defaults were chosen from, selected
                    by the environment switches of DESIGN.md's appendix.  Same ABI.  Loaded by the tests / A-B tools only (DKT_TWINS=1 + a variant switch);
   libdkt_diag.so   measurement-only kernels (stream ceilings, co-residency spinners, the round-1 register-sweep kernel).
@@ -34,6 +36,10 @@ TWINS_LIB_PATH = os.path.join(_HERE, "libdkt_twins.so")
 # 16-bit trunk features (mixed-precision backbones): product code, a library of its own (include/dkt_abi_x16.h)
 X16_SOURCES = ["dkt_frontend_x16.hip"]
 X16_LIB_PATH = os.path.join(_HERE, "libdkt_x16.so")
+# the image-dataset loader's episode transform: product code, a library of its own (include/dkt_abi_data.h)
+DATA_SOURCES = ["dkt_augment.hip"]
+DATA_LIB_PATH = os.path.join(_HERE, "libdkt_data.so")
+DATA_HEADER = os.path.join(INCLUDE, "dkt_abi_data.h")
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(INCLUDE, "dkt_abi.h"), os.path.join(INCLUDE, "dkt_abi_x16.h")]
 OBJ_DIR = os.path.join(_HERE, "build")
 
@@ -95,6 +101,14 @@ X16_SIGNATURES = {
     "dkt_affine_normalize_x16": (_c_i, [_c_p, _c_i, _c_p, _c_p, ctypes.c_long, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p]),
     "dkt_normalize_bn_bwd_x16": (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_p, ctypes.c_long, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p]),
 }
+
+# libdkt_data.so (include/dkt_abi_data.h; tests check that this lists every function of the header)
+DATA_SIGNATURES = {
+    "dkt_data_abi_version": (_c_i, []),
+    "dkt_augment_plan": (_c_i, [_c_p, _c_i, _c_i, ctypes.POINTER(ctypes.c_size_t)]),
+    "dkt_augment_u8": (_c_i, [_c_p, ctypes.c_size_t, _c_p, _c_p, _c_i, _c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
+}
+AUG_COLS = 12
 
 _lock = threading.Lock()
 _libs = {}          # path -> bound CDLL
@@ -168,7 +182,7 @@ def _digest(src: str, twins: bool = False) -> str:
     """Content hash of a source, every header and the flags: the object cache key (mtimes do not survive a checkout)."""
     import hashlib
     h = hashlib.sha256()
-    for f in [src] + HEADERS:
+    for f in [src] + HEADERS + ([DATA_HEADER] if os.path.basename(src) in DATA_SOURCES else []):
         with open(f, "rb") as fh:
             h.update(fh.read())
     h.update(" ".join(_flags(twins)).encode())
@@ -241,7 +255,7 @@ def _compile_link(sources, target, replace=None, verbose=False, twins: bool = Fa
                     keep.update(json.load(fh))
         for f in os.listdir(OBJ_DIR):
             base = f[:-len(".res.json")] if f.endswith(".res.json") else f
-            if base.endswith(".o") and base not in keep and any(base.startswith(src + ".") for src in SOURCES + DIAG_SOURCES + X16_SOURCES):
+            if base.endswith(".o") and base not in keep and any(base.startswith(src + ".") for src in SOURCES + DIAG_SOURCES + X16_SOURCES + DATA_SOURCES):
                 try:
                     os.remove(os.path.join(OBJ_DIR, f))
                 except OSError:
@@ -255,6 +269,7 @@ def build(force: bool = False, verbose: bool = False, out: str = None, replace: 
     variant library for A/B runs (the product library only)."""
     if out is None and not force and not needs_build():
         build_x16(verbose)
+        build_data(verbose)
         return LIB_PATH
     if force and os.path.isdir(OBJ_DIR):
         for f in os.listdir(OBJ_DIR):
@@ -263,6 +278,7 @@ def build(force: bool = False, verbose: bool = False, out: str = None, replace: 
     path = _compile_link(SOURCES, out or LIB_PATH, replace, verbose)
     if out is None:
         build_x16(verbose)
+        build_data(verbose)
     return path
 
 
@@ -278,6 +294,20 @@ def build_x16(verbose: bool = False) -> str:
     if not x16_needs_build():
         return X16_LIB_PATH
     return _compile_link(X16_SOURCES, X16_LIB_PATH, None, verbose)
+
+
+def data_needs_build() -> bool:
+    if not os.path.exists(DATA_LIB_PATH) or not os.path.exists(DATA_LIB_PATH + ".stamp"):
+        return True
+    with open(DATA_LIB_PATH + ".stamp") as fh:
+        return fh.read() != _stamp(DATA_SOURCES)
+
+
+def build_data(verbose: bool = False) -> str:
+    """The episode image-transform library libdkt_data.so (product code: the spill check applies, budget 0)."""
+    if not data_needs_build():
+        return DATA_LIB_PATH
+    return _compile_link(DATA_SOURCES, DATA_LIB_PATH, None, verbose)
 
 
 def build_twins(verbose: bool = False) -> str:
@@ -515,6 +545,46 @@ def load_x16() -> ctypes.CDLL:
         want, got = x16_abi_version_of_header(), int(lib.dkt_x16_abi_version())
         if got != want:
             raise RuntimeError("%s implements DKT_X16_ABI_VERSION %d, include/dkt_abi_x16.h declares %d: rebuild" % (path, got, want))
+        _libs[path] = lib
+        return lib
+
+
+_data_checked = False
+
+
+def data_abi_version_of_header() -> int:
+    """DKT_DATA_ABI_VERSION as include/dkt_abi_data.h declares it."""
+    import re
+    with open(DATA_HEADER) as fh:
+        return int(re.search(r"#define\s+DKT_DATA_ABI_VERSION\s+(\d+)", fh.read()).group(1))
+
+
+def load_data() -> ctypes.CDLL:
+    """dlopen libdkt_data.so and bind every function of include/dkt_abi_data.h; built on first use where the sources are present.  Raises (never
+    falls back) when it cannot be built or loaded."""
+    global _data_checked
+    if not _data_checked:
+        if os.path.isdir(CSRC):
+            build_data()
+        _data_checked = True
+    path = DATA_LIB_PATH
+    with _lock:
+        lib = _libs.get(path)
+        if lib is not None:
+            return lib
+        if not os.path.exists(path):
+            raise RuntimeError("%s is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` -- image datasets have no CPU fallback." % path)
+        lib = ctypes.CDLL(path)
+        for name, (res, args) in DATA_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise RuntimeError("%s lacks symbol %s declared in include/dkt_abi_data.h" % (os.path.basename(path), name)) from e
+            fn.restype = res
+            fn.argtypes = args
+        want, got = data_abi_version_of_header(), int(lib.dkt_data_abi_version())
+        if got != want:
+            raise RuntimeError("%s implements DKT_DATA_ABI_VERSION %d, include/dkt_abi_data.h declares %d: rebuild" % (path, got, want))
         _libs[path] = lib
         return lib
 

@@ -12,5 +12,5 @@ amp = None
 
 save_dir = './save/'                     # checkpoints: <save_dir>checkpoints/<dataset>/<model>_<method>[_aug]_<n>way_<k>shot
 
-# file-list roots of the image datasets (only used when such a tree and torchvision are present; `--dataset synthetic` needs none)
+# file-list roots of the image datasets (image_data.FilelistEpisodeLoader; `--dataset synthetic` needs none)
 data_dir = {name: './filelists/%s/' % name for name in ('CUB', 'miniImagenet', 'omniglot', 'emnist')}

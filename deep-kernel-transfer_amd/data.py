@@ -1,6 +1,6 @@
 """Episodic loaders.  The reference's SetDataManager (data/datamgr.py:68-84) reads JSON file lists of image
-datasets through torchvision; neither the datasets nor torchvision exist here (data/ is
-out of scope), so the drivers run on a SYNTHETIC episodic source with the same output contract:
+datasets through torchvision; here those datasets go through image_data.FilelistEpisodeLoader (HIP transform, no
+torchvision), and `--dataset synthetic`, the default, draws from a SYNTHETIC episodic source with the same output contract:
 an iterable of length n_episode yielding (x, y) with x: float32 [n_way, n_support + n_query, 3, H, W] on the CPU
 and y: [n_way, n_support + n_query] global class ids, classes drawn by torch.randperm(n_classes)[:n_way]
 (EpisodicBatchSampler, data/dataset.py:76-87)."""
@@ -47,12 +47,16 @@ class SyntheticEpisodeLoader:
             yield torch.stack(xs), torch.stack(ys)
 
 
-def get_episode_loader(params, split, n_way, n_support, n_query, n_episode, image_size, seed=0):
-    """split in {'base', 'val', 'novel'}.  Real datasets need the reference's filelists + torchvision."""
+def get_episode_loader(params, split, n_way, n_support, n_query, n_episode, image_size, seed=0, aug=False):
+    """split in {'base', 'val', 'novel'}.  `--dataset synthetic` draws SyntheticEpisodeLoader episodes; the reference's image datasets (CUB,
+    miniImagenet, omniglot, emnist, cross, cross_char) read the file list the reference would (configs.data_dir) through
+    image_data.FilelistEpisodeLoader, with the training transform when `aug` (train.py: --train_aug, base split only), else the evaluation one."""
     if params.dataset != 'synthetic':
-        raise NotImplementedError(
-            "dataset '%s': the image datasets of the reference (filelists/, torchvision transforms) are not part of "
-            "this build; use --dataset synthetic" % params.dataset)
+        from .image_data import DATASETS, FilelistEpisodeLoader, filelist_for, filelist_path
+        if params.dataset not in DATASETS:
+            raise NotImplementedError("dataset '%s': not an episodic image dataset (%s, or synthetic)" % (params.dataset, ', '.join(DATASETS)))
+        return FilelistEpisodeLoader(filelist_path(params.dataset, split), n_way, n_support, n_query, n_episode, image_size, aug=aug, seed=seed,
+                                     dataset_key=filelist_for(params.dataset, split)[0])
     offsets = {'base': 0, 'val': 64, 'novel': 96}
     sizes = {'base': 64, 'val': 32, 'novel': 40}
     return SyntheticEpisodeLoader(n_way, n_support, n_query, n_episode, image_size, n_classes=max(sizes[split], n_way),

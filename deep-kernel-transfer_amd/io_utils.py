@@ -1,8 +1,8 @@
 """Command-line flags and checkpoint-path helpers with the reference's names and defaults
 (reference io_utils.py:17-47 parse_args, :66-86 get_assigned_file / get_resume_file / get_best_file).
 Only the DKT method is built; `--dataset synthetic` (default here: no datasets exist in this environment)
-draws class-structured random episodes, the dataset names of the reference are accepted when a
-`filelists/<dataset>/{base,val,novel}.json` tree and torchvision are present."""
+draws class-structured random episodes, the dataset names of the reference read its file lists from
+configs.data_dir (image_data.FilelistEpisodeLoader)."""
 from __future__ import annotations
 
 import argparse

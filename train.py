@@ -77,7 +77,7 @@ def main(argv=None):
     n_query = max(1, int(16 * params.test_n_way / params.train_n_way))
     n_ep = params.n_episode or 100
     base_loader = get_episode_loader(params, 'base', params.train_n_way, params.n_shot, n_query, n_ep, image_size,
-                                     seed=params.seed + 100 * distributed.rank())
+                                     seed=params.seed + 100 * distributed.rank(), aug=params.train_aug)
     # validation episodes are sharded like test.py's: rank r evaluates its own len(shard) episodes (rank-dependent seed) and
     # DKT.test_loop gathers the per-episode accuracies -- n_ep independent episodes in total, not W copies of the same ones
     val_shard = distributed.shard_episodes(n_ep)
