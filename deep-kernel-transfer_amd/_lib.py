@@ -3,13 +3,15 @@
 There is NO CPU fallback: every entry point of `ops` goes through this library, and `load()`
 raises if the shared object is missing or a symbol of the header is absent.
 
-Four in-tree shared objects, all hipcc --offload-arch=gfx950:
+Six in-tree shared objects, all hipcc --offload-arch=gfx950:
   libdkt_hip.so    the PRODUCT: the default kernel of every call, no measurement switch, no variant instantiation;
   libdkt_x16.so    also product code: the six front-end calls for 16-bit (bf16 / f16) trunk features of a mixed-precision backbone (include/dkt_abi_x16.h,
                    csrc/dkt_frontend_x16.hip: the fp32 front-end templates instantiated for 16-bit X / dX).  A library of its own so that the product
                    library's ABI and kernel list stay as they are;
   libdkt_data.so   the episode image transform of the image-dataset loader (include/dkt_abi_data.h, csrc/dkt_augment.hip: Pillow's bilinear resize,
                    ImageEnhance jitter, flip, ToTensor + Normalize, bit for bit).  A library of its own, like libdkt_x16.so;
+  libdkt_smk.so    the spectral-mixture kernel for many small tasks of the sine-wave experiment (include/dkt_abi_smk.h, csrc/dkt_smk_task.hip: a
+                   workgroup per task or tasks, a lane per matrix entry).  A library of its own, like libdkt_x16.so;
   libdkt_twins.so  the same sources with -DDKT_TWINS: every pipeline variant, legacy pipeline and validation twin the defaults were chosen from, selected
                    by the environment switches of DESIGN.md's appendix.  Same ABI.  Loaded by the tests / A-B tools only (DKT_TWINS=1 + a variant switch);
   libdkt_diag.so   measurement-only kernels (stream ceilings, co-residency spinners, the round-1 register-sweep kernel).
@@ -40,6 +42,10 @@ X16_LIB_PATH = os.path.join(_HERE, "libdkt_x16.so")
 DATA_SOURCES = ["dkt_augment.hip"]
 DATA_LIB_PATH = os.path.join(_HERE, "libdkt_data.so")
 DATA_HEADER = os.path.join(INCLUDE, "dkt_abi_data.h")
+# the task-resident spectral-mixture kernels of the sine-wave experiment: product code, a library of its own (include/dkt_abi_smk.h)
+SMK_SOURCES = ["dkt_smk_task.hip"]
+SMK_LIB_PATH = os.path.join(_HERE, "libdkt_smk.so")
+SMK_HEADER = os.path.join(INCLUDE, "dkt_abi_smk.h")
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(INCLUDE, "dkt_abi.h"), os.path.join(INCLUDE, "dkt_abi_x16.h")]
 OBJ_DIR = os.path.join(_HERE, "build")
 
@@ -109,6 +115,15 @@ DATA_SIGNATURES = {
     "dkt_augment_u8": (_c_i, [_c_p, ctypes.c_size_t, _c_p, _c_p, _c_i, _c_p, _c_p, _c_i, _c_p, _c_p, _c_p, _c_p, ctypes.c_size_t, _c_p]),
 }
 AUG_COLS = 12
+
+# libdkt_smk.so (include/dkt_abi_smk.h; tests check that this lists every function of the header)
+SMK_SIGNATURES = {
+    "dkt_smk_abi_version": (_c_i, []),
+    "dkt_smk_task_f32": (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_p]),
+    "dkt_smk_task_workspace_bytes": (ctypes.c_size_t, [_c_i, _c_i, _c_i, _c_i]),
+    "dkt_smk_task_bwd_f32": (_c_i, [_c_p] * 10 + [_c_i, _c_i, _c_i, _c_i, _c_p]),
+}
+SMK_MAX_N, SMK_MAX_M, SMK_MAX_D, SMK_MAX_Q = 32, 256, 64, 8      # the limits of include/dkt_abi_smk.h (DKT_ERR_SHAPE outside them)
 
 _lock = threading.Lock()
 _libs = {}          # path -> bound CDLL
@@ -182,7 +197,8 @@ def _digest(src: str, twins: bool = False) -> str:
     """Content hash of a source, every header and the flags: the object cache key (mtimes do not survive a checkout)."""
     import hashlib
     h = hashlib.sha256()
-    for f in [src] + HEADERS + ([DATA_HEADER] if os.path.basename(src) in DATA_SOURCES else []):
+    extra = [DATA_HEADER] if os.path.basename(src) in DATA_SOURCES else [SMK_HEADER] if os.path.basename(src) in SMK_SOURCES else []
+    for f in [src] + HEADERS + extra:
         with open(f, "rb") as fh:
             h.update(fh.read())
     h.update(" ".join(_flags(twins)).encode())
@@ -255,7 +271,7 @@ def _compile_link(sources, target, replace=None, verbose=False, twins: bool = Fa
                     keep.update(json.load(fh))
         for f in os.listdir(OBJ_DIR):
             base = f[:-len(".res.json")] if f.endswith(".res.json") else f
-            if base.endswith(".o") and base not in keep and any(base.startswith(src + ".") for src in SOURCES + DIAG_SOURCES + X16_SOURCES + DATA_SOURCES):
+            if base.endswith(".o") and base not in keep and any(base.startswith(src + ".") for src in SOURCES + DIAG_SOURCES + X16_SOURCES + DATA_SOURCES + SMK_SOURCES):
                 try:
                     os.remove(os.path.join(OBJ_DIR, f))
                 except OSError:
@@ -270,6 +286,7 @@ def build(force: bool = False, verbose: bool = False, out: str = None, replace: 
     if out is None and not force and not needs_build():
         build_x16(verbose)
         build_data(verbose)
+        build_smk(verbose)
         return LIB_PATH
     if force and os.path.isdir(OBJ_DIR):
         for f in os.listdir(OBJ_DIR):
@@ -279,6 +296,7 @@ def build(force: bool = False, verbose: bool = False, out: str = None, replace: 
     if out is None:
         build_x16(verbose)
         build_data(verbose)
+        build_smk(verbose)
     return path
 
 
@@ -308,6 +326,20 @@ def build_data(verbose: bool = False) -> str:
     if not data_needs_build():
         return DATA_LIB_PATH
     return _compile_link(DATA_SOURCES, DATA_LIB_PATH, None, verbose)
+
+
+def smk_needs_build() -> bool:
+    if not os.path.exists(SMK_LIB_PATH) or not os.path.exists(SMK_LIB_PATH + ".stamp"):
+        return True
+    with open(SMK_LIB_PATH + ".stamp") as fh:
+        return fh.read() != _stamp(SMK_SOURCES)
+
+
+def build_smk(verbose: bool = False) -> str:
+    """The task-resident spectral-mixture library libdkt_smk.so (product code: the spill check applies, budget 0)."""
+    if not smk_needs_build():
+        return SMK_LIB_PATH
+    return _compile_link(SMK_SOURCES, SMK_LIB_PATH, None, verbose)
 
 
 def build_twins(verbose: bool = False) -> str:
@@ -589,12 +621,52 @@ def load_data() -> ctypes.CDLL:
         return lib
 
 
+_smk_checked = False
+
+
+def smk_abi_version_of_header() -> int:
+    """DKT_SMK_ABI_VERSION as include/dkt_abi_smk.h declares it."""
+    import re
+    with open(SMK_HEADER) as fh:
+        return int(re.search(r"#define\s+DKT_SMK_ABI_VERSION\s+(\d+)", fh.read()).group(1))
+
+
+def load_smk() -> ctypes.CDLL:
+    """dlopen libdkt_smk.so and bind every function of include/dkt_abi_smk.h; built on first use where the sources are present.  Raises (never
+    falls back) when it cannot be built or loaded."""
+    global _smk_checked
+    if not _smk_checked:
+        if os.path.isdir(CSRC):
+            build_smk()
+        _smk_checked = True
+    path = SMK_LIB_PATH
+    with _lock:
+        lib = _libs.get(path)
+        if lib is not None:
+            return lib
+        if not os.path.exists(path):
+            raise RuntimeError("%s is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` -- there is no CPU fallback." % path)
+        lib = ctypes.CDLL(path)
+        for name, (res, args) in SMK_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise RuntimeError("%s lacks symbol %s declared in include/dkt_abi_smk.h" % (os.path.basename(path), name)) from e
+            fn.restype = res
+            fn.argtypes = args
+        want, got = smk_abi_version_of_header(), int(lib.dkt_smk_abi_version())
+        if got != want:
+            raise RuntimeError("%s implements DKT_SMK_ABI_VERSION %d, include/dkt_abi_smk.h declares %d: rebuild" % (path, got, want))
+        _libs[path] = lib
+        return lib
+
+
 def load_diag() -> ctypes.CDLL:
     """dlopen the measurement-only library (tools / tests); builds it on first use."""
     return ctypes.CDLL(build_diag())
 
 
-STATUS = {0: "DKT_OK", -1: "DKT_ERR_BAD_ARG", -2: "DKT_ERR_TOO_LARGE", -3: "DKT_ERR_WORKSPACE", -4: "DKT_ERR_LAUNCH"}
+STATUS = {0: "DKT_OK", -1: "DKT_ERR_BAD_ARG", -2: "DKT_ERR_TOO_LARGE", -3: "DKT_ERR_WORKSPACE", -4: "DKT_ERR_LAUNCH", -5: "DKT_ERR_SHAPE"}
 
 
 def check(status: int, what: str) -> None:

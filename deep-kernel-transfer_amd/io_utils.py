@@ -82,6 +82,27 @@ def parse_args_regression(script, argv=None):
     return _apply_amp(parser.parse_args(argv))
 
 
+def parse_args_sines(argv=None):
+    """Flags of train_sines.py.  The defaults are the constants of the reference's sines/train_DKT.py (:143-160, :186): 50000 iterations,
+    10 training shots, 5 test shots, Adam at lr 1e-3 for the GP and the network, 500 test tasks, one task per step."""
+    parser = argparse.ArgumentParser(description='sine-wave regression with DKT')
+    parser.add_argument('--seed', default=0, type=int, help='Seed of the network initialisation and of the task samplers. Default: 0')
+    parser.add_argument('--iterations', default=50000, type=int, help='training steps (tot_iterations)')
+    parser.add_argument('--n_shot_train', default=10, type=int, help='points per training task')
+    parser.add_argument('--n_shot_test', default=5, type=int, help='support points per test task')
+    parser.add_argument('--n_test_tasks', default=500, type=int, help='test tasks (one batch)')
+    parser.add_argument('--lr', default=1e-3, type=float, help='Adam learning rate of both parameter groups')
+    parser.add_argument('--test_range', default='in', choices=['in', 'out'], help='in: (-5, 5); out: (-5, 10), the out-of-range condition')
+    parser.add_argument('--family', default='sine', choices=['sine', 'cosine'], help='task family of training and test')
+    parser.add_argument('--tasks_per_step', default=1, type=int, help='[this build] tasks per Adam step (1 = the reference)')
+    parser.add_argument('--checkpoint', default=None, help='save the model here after training (with --test_only: load it from here)')
+    parser.add_argument('--test_only', action='store_true', help='skip training: load --checkpoint and run the test phase')
+    args = parser.parse_args(argv)
+    if args.test_only and not args.checkpoint:
+        parser.error('--test_only needs --checkpoint')
+    return args
+
+
 def get_assigned_file(checkpoint_dir, num):
     return os.path.join(checkpoint_dir, '{:d}.tar'.format(num))
 

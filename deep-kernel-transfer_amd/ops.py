@@ -509,6 +509,100 @@ def spectral_mixture_matrix(z: torch.Tensor, weights: torch.Tensor, means: torch
     return _SpectralMixtureFn.apply(z, weights, means, scales)
 
 
+# task-resident spectral mixture (libdkt_smk.so, include/dkt_abi_smk.h): many small tasks, a lane per entry, no Eq round trip
+def smk_task_supported(m: int, n: int, d: int, q: int, symmetric: bool = True) -> bool:
+    """Whether dkt_smk_task_f32 (symmetric: N <= 32; cross: M <= 256, N <= 32) and, when symmetric, its backward take this shape."""
+    return (1 <= n <= _lib.SMK_MAX_N and 1 <= m <= (_lib.SMK_MAX_N if symmetric else _lib.SMK_MAX_M) and 1 <= d <= _lib.SMK_MAX_D
+            and 1 <= q <= _lib.SMK_MAX_Q)
+
+
+def _smk_hypers(weights, means, scales, d: int):
+    weights = _req(weights.reshape(-1), "weights", 1)
+    q = weights.numel()
+    means = _req(means.reshape(q, -1), "means", 2)
+    scales = _req(scales.reshape(q, -1), "scales", 2)
+    if means.shape[1] != d or scales.shape[1] != d:
+        raise RuntimeError("smk_task: means / scales must be [Q,D] with D = %d" % d)
+    return weights, means, scales, q
+
+
+def smk_task(x1: torch.Tensor, x2: Optional[torch.Tensor], weights: torch.Tensor, means: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """Spectral-mixture matrix E[b] = k(x1[b], x2[b]) of libdkt_smk.so (x2 None: symmetric, exactly); the arguments of `smk`.  A shape outside
+    the library's limits raises (DKT_ERR_SHAPE): `smk_task_supported` tells beforehand."""
+    x1 = _req(x1, "x1", 3)
+    b_, m, d = x1.shape
+    if x2 is not None:
+        x2 = _req(x2, "x2", 3)
+        if x2.shape[0] != b_ or x2.shape[2] != d:
+            raise RuntimeError("smk_task: shape mismatch %s vs %s" % (tuple(x1.shape), tuple(x2.shape)))
+        n = x2.shape[1]
+    else:
+        n = m
+    weights, means, scales, q = _smk_hypers(weights, means, scales, d)
+    e = torch.empty((b_, m, n), device=x1.device, dtype=torch.float32)
+    with _timed("dkt_smk_task_f32"):
+        st = _lib.load_smk().dkt_smk_task_f32(_p(x1), _p(x2), _p(weights), _p(means), _p(scales), _p(e), b_, m, n, d, q, _stream())
+    _lib.check(st, "dkt_smk_task_f32")
+    return e
+
+
+def smk_task_bwd(ge: torch.Tensor, x: torch.Tensor, weights: torch.Tensor, means: torch.Tensor, scales: torch.Tensor):
+    """Chain rule of the symmetric task-resident matrix: (dx [B,N,D], dweights [Q], dmeans [Q,D], dscales [Q,D]), the hyper-parameter
+    gradients summed over the B tasks inside the library (fixed order, bitwise reproducible)."""
+    x = _req(x, "x", 3)
+    b_, n, d = x.shape
+    ge = _req(ge, "ge", 3)
+    if tuple(ge.shape) != (b_, n, n):
+        raise RuntimeError("smk_task_bwd: ge must be [B,N,N] = %s, got %s" % ((b_, n, n), tuple(ge.shape)))
+    weights, means, scales, q = _smk_hypers(weights, means, scales, d)
+    lib = _lib.load_smk()
+    dx = torch.empty_like(x)
+    dw = torch.empty((q,), device=x.device, dtype=torch.float32)
+    dm = torch.empty((q, d), device=x.device, dtype=torch.float32)
+    ds = torch.empty((q, d), device=x.device, dtype=torch.float32)
+    ws = torch.empty((max(int(lib.dkt_smk_task_workspace_bytes(b_, n, d, q)), 4) // 4,), device=x.device, dtype=torch.float32)
+    with _timed("dkt_smk_task_bwd_f32"):
+        st = lib.dkt_smk_task_bwd_f32(_p(ge), _p(x), _p(weights), _p(means), _p(scales), _p(dx), _p(dw), _p(dm), _p(ds), _p(ws), b_, n, d, q,
+                                      _stream())
+    _lib.check(st, "dkt_smk_task_bwd_f32")
+    return dx, dw, dm, ds
+
+
+class _SpectralMixtureTaskFn(torch.autograd.Function):
+    """E = SpectralMixtureKernel(z, z) of libdkt_smk.so, differentiable in z, the mixture weights, means and scales."""
+
+    @staticmethod
+    def forward(ctx, z, weights, means, scales):
+        e = smk_task(z, None, weights, means, scales)
+        ctx.save_for_backward(z, weights, means, scales)
+        return e
+
+    @staticmethod
+    def backward(ctx, ge):
+        z, weights, means, scales = ctx.saved_tensors
+        dz, dw, dm, ds = smk_task_bwd(ge.contiguous(), z, weights, means, scales)
+        need = ctx.needs_input_grad
+        return (dz if need[0] else None, dw.reshape(weights.shape) if need[1] else None, dm.reshape(means.shape) if need[2] else None,
+                ds.reshape(scales.shape) if need[3] else None)
+
+
+def spectral_mixture_matrix_task(z: torch.Tensor, weights: torch.Tensor, means: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """`spectral_mixture_matrix` for many small tasks (libdkt_smk.so); a shape outside that library's limits takes `spectral_mixture_matrix`."""
+    z = _req(z, "z", 3)
+    if not smk_task_supported(z.shape[1], z.shape[1], z.shape[2], weights.numel(), True):
+        return spectral_mixture_matrix(z, weights, means, scales)
+    return _SpectralMixtureTaskFn.apply(z, weights, means, scales)
+
+
+def smk_any(x1: torch.Tensor, x2: Optional[torch.Tensor], weights: torch.Tensor, means: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """Forward only: `smk_task` where its limits allow, else the product library's `smk`."""
+    m, d = x1.shape[1], x1.shape[2]
+    n = m if x2 is None else x2.shape[1]
+    if smk_task_supported(m, n, d, weights.numel(), x2 is None):
+        return smk_task(x1, x2, weights, means, scales)
+    return smk(x1, x2, weights, means, scales)[0]
+
+
 CLASSMAP_RBF, CLASSMAP_MATERN25, CLASSMAP_POLY = 0, 1, 2
 
 
