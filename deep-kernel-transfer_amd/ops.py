@@ -376,13 +376,21 @@ def predict(ex: torch.Tensor, alpha: torch.Tensor, sv: torch.Tensor, mean: torch
 
 
 def predict_var(ex: torch.Tensor, exx: torch.Tensor, chol: torch.Tensor, sv: torch.Tensor, noise: torch.Tensor):
+    """var[b,c,q] = sv[c] exx[b,q] - sv[c]^2 |L[b,c]^-1 ex[b,q]|^2 + noise[c] (dkt_predict_var_f32).
+    ex: [B,M,N] base cross kernel, exx: [B,M] its prior diagonal k(x*, x*), chol: [B,C,N,N] lower factors of mll(want_chol=True); sv, noise: C elements."""
     ex = _req(ex, "ex", 3)
     exx = _req(exx, "exx", 2)
     chol = _req(chol, "chol", 4)
     b_, m, n = ex.shape
     c_ = chol.shape[1]
+    if tuple(exx.shape) != (b_, m):
+        raise RuntimeError("predict_var: exx must be [B,M] = %s for ex %s, got %s" % ((b_, m), tuple(ex.shape), tuple(exx.shape)))
+    if chol.shape[0] != b_ or chol.shape[2] != n or chol.shape[3] != n:
+        raise RuntimeError("predict_var: chol must be [B,C,N,N] with B=%d, N=%d of ex %s, got %s" % (b_, n, tuple(ex.shape), tuple(chol.shape)))
     sv = _req(sv.reshape(-1), "sv", 1)
     noise = _req(noise.reshape(-1), "noise", 1)
+    if not (sv.numel() == noise.numel() == c_):
+        raise RuntimeError("predict_var: sv/noise must have C=%d elements, got %d / %d" % (c_, sv.numel(), noise.numel()))
     var = torch.empty((b_, c_, m), device=ex.device, dtype=torch.float32)
     lib = _lib_now()
     _lib.check(lib.dkt_predict_var_f32(_p(ex), _p(exx), _p(chol), _p(sv), _p(noise), _p(var), b_, c_, m, n, _stream()),
