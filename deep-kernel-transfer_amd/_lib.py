@@ -1,20 +1,23 @@
-"""Build + ctypes binding of libdkt_hip.so (the C ABI declared in include/dkt_abi.h).
+"""Build + ctypes binding of the project's HIP shared objects: one `LibSpec` per library in the table `LIBS`, and ONE implementation of each operation
+(staleness check, build-if-stale, header-version reader, load) that takes a spec.  The per-library names (`load_x16()`, `build_smk()`, `X16_LIB_PATH`, ...) are
+one-line views of the table.
 
-There is NO CPU fallback: every entry point of `ops` goes through this library, and `load()`
-raises if the shared object is missing or a symbol of the header is absent.
+There is NO CPU fallback: every entry point of `ops` goes through these libraries, and loading raises if a shared object is missing, lacks a symbol of its
+header or implements another ABI version than the header declares.
 
 Six in-tree shared objects, all hipcc --offload-arch=gfx950:
-  libdkt_hip.so    the PRODUCT: the default kernel of every call, no measurement switch, no variant instantiation;
-  libdkt_x16.so    also product code: the six front-end calls for 16-bit (bf16 / f16) trunk features of a mixed-precision backbone (include/dkt_abi_x16.h,
-                   csrc/dkt_frontend_x16.hip: the fp32 front-end templates instantiated for 16-bit X / dX).  A library of its own so that the product
-                   library's ABI and kernel list stay as they are;
-  libdkt_data.so   the episode image transform of the image-dataset loader (include/dkt_abi_data.h, csrc/dkt_augment.hip: Pillow's bilinear resize,
-                   ImageEnhance jitter, flip, ToTensor + Normalize, bit for bit).  A library of its own, like libdkt_x16.so;
-  libdkt_smk.so    the spectral-mixture kernel for many small tasks of the sine-wave experiment (include/dkt_abi_smk.h, csrc/dkt_smk_task.hip: a
-                   workgroup per task or tasks, a lane per matrix entry).  A library of its own, like libdkt_x16.so;
-  libdkt_twins.so  the same sources with -DDKT_TWINS: every pipeline variant, legacy pipeline and validation twin the defaults were chosen from, selected
-                   by the environment switches of DESIGN.md's appendix.  Same ABI.  Loaded by the tests / A-B tools only (DKT_TWINS=1 + a variant switch);
-  libdkt_diag.so   measurement-only kernels (stream ceilings, co-residency spinners, the round-1 register-sweep kernel).
+  hip    libdkt_hip.so    the PRODUCT (include/dkt_abi.h): the default kernel of every call, no measurement switch, no variant instantiation;
+  x16    libdkt_x16.so    product code: the front-end calls for 16-bit (bf16 / f16) trunk features (include/dkt_abi_x16.h); apart so that the product ABI stays as it is;
+  data   libdkt_data.so   product code: the episode image transform of the image-dataset loader (include/dkt_abi_data.h); apart for the same reason;
+  smk    libdkt_smk.so    product code: the task-resident spectral-mixture kernels of the sine-wave experiment (include/dkt_abi_smk.h); apart for the same reason;
+  twins  libdkt_twins.so  the product's sources with -DDKT_TWINS: every pipeline variant and validation twin the defaults were chosen from, selected by the
+                          environment switches of DESIGN.md's appendix.  Same ABI.  Tests and A/B tools only (DKT_TWINS=1 + a variant switch);
+  diag   libdkt_diag.so   measurement-only kernels (stream ceilings, co-residency spinners, the round-1 register-sweep kernel): no header, no version.
+
+An object file's cache key hashes its source, every csrc/*.h and csrc/*.inc, include/dkt_abi.h and the ABI header of its own library -- what the sources
+include -- so an edit to one library's header recompiles that library only.
+
+Adding a library: one ABI header under include/, one signature dict, one `LibSpec` entry in `LIBS` (+ the one-line `load_*` / `build_*` names its callers want).
 """
 from __future__ import annotations
 
@@ -23,30 +26,14 @@ import json
 import os
 import subprocess
 import threading
+from typing import NamedTuple, Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(_ROOT, "include")
-LIB_PATH = os.path.join(_HERE, "libdkt_hip.so")
 SOURCES = ["dkt_gram.hip", "dkt_gram_ep.hip", "dkt_gram_big.hip", "dkt_gram_small.hip", "dkt_classkernel.hip", "dkt_mll.hip", "dkt_mll_mfma.hip", "dkt_mll_h2.hip", "dkt_mll_reg.hip", "dkt_mll_big.hip", "dkt_mll_tiled.hip", "dkt_mll_band.hip", "dkt_objective.hip", "dkt_predict.hip",
            "dkt_spectral.hip", "dkt_frontend.hip", "dkt_frontend_big.hip", "dkt_lowrank.hip"]
-# measurement-only kernels (stream ceilings, co-residency spinners): a separate test / tooling library, NOT part of the product
-DIAG_SOURCES = ["dkt_diag.hip", "dkt_mll_reg_twin.hip"]
-DIAG_LIB_PATH = os.path.join(_HERE, "libdkt_diag.so")
-TWINS_LIB_PATH = os.path.join(_HERE, "libdkt_twins.so")
-# 16-bit trunk features (mixed-precision backbones): product code, a library of its own (include/dkt_abi_x16.h)
-X16_SOURCES = ["dkt_frontend_x16.hip"]
-X16_LIB_PATH = os.path.join(_HERE, "libdkt_x16.so")
-# the image-dataset loader's episode transform: product code, a library of its own (include/dkt_abi_data.h)
-DATA_SOURCES = ["dkt_augment.hip"]
-DATA_LIB_PATH = os.path.join(_HERE, "libdkt_data.so")
-DATA_HEADER = os.path.join(INCLUDE, "dkt_abi_data.h")
-# the task-resident spectral-mixture kernels of the sine-wave experiment: product code, a library of its own (include/dkt_abi_smk.h)
-SMK_SOURCES = ["dkt_smk_task.hip"]
-SMK_LIB_PATH = os.path.join(_HERE, "libdkt_smk.so")
-SMK_HEADER = os.path.join(INCLUDE, "dkt_abi_smk.h")
-HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(INCLUDE, "dkt_abi.h"), os.path.join(INCLUDE, "dkt_abi_x16.h")]
 OBJ_DIR = os.path.join(_HERE, "build")
 
 _c_p = ctypes.c_void_p
@@ -125,8 +112,46 @@ SMK_SIGNATURES = {
 }
 SMK_MAX_N, SMK_MAX_M, SMK_MAX_D, SMK_MAX_Q = 32, 256, 64, 8      # the limits of include/dkt_abi_smk.h (DKT_ERR_SHAPE outside them)
 
+# libdkt_diag.so has no header: the entries below are bound at load, and callers of its other exports (tools, tests) set their own argtypes on the handle
+DIAG_SIGNATURES = {
+    "dkt_diag_mll_reg_f32": (_c_i, [_c_p, _c_p, ctypes.c_long, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_f, _c_i, ctypes.c_uint] + [_c_p] * 11),
+}
+
+
+class LibSpec(NamedTuple):
+    """What differs between the libraries; everything below takes one of these."""
+    path: str                               # the shared object
+    sources: list                           # names under csrc/
+    signatures: dict                        # name -> (restype, argtypes), bound at load
+    no_fallback: str                        # the last sentence of its not-built error
+    header: Optional[str] = None            # its ABI header under include/: hashed into its objects; `signatures` lists every function of it (tests check this)
+    version_macro: Optional[str] = None     # ... as the header defines it
+    version_symbol: Optional[str] = None    # ... as the library reports it
+    reload_symbol: Optional[str] = None     # makes the library re-read its environment switches (ops._sync_env)
+    twins: bool = False                     # compiled with -DDKT_TWINS
+    spill_budget: bool = True               # SPILL_BUDGET fails the build: product code (not the twins' non-default instantiations, not measurement kernels)
+
+
+def _so(stem: str) -> str:
+    return os.path.join(_HERE, "libdkt_%s.so" % stem)
+
+
+_ABI = dict(header="dkt_abi.h", version_macro="DKT_ABI_VERSION", version_symbol="dkt_abi_version", reload_symbol="dkt_reload_env",
+            signatures=SIGNATURES, no_fallback="the DKT hot path has no CPU fallback.")
+LIBS = {
+    "hip": LibSpec(_so("hip"), SOURCES, **_ABI),
+    "twins": LibSpec(_so("twins"), SOURCES, twins=True, spill_budget=False, **_ABI),
+    "x16": LibSpec(_so("x16"), ["dkt_frontend_x16.hip"], X16_SIGNATURES, "16-bit trunk features have no fallback.", "dkt_abi_x16.h", "DKT_X16_ABI_VERSION",
+                   "dkt_x16_abi_version", "dkt_x16_reload_env"),
+    "data": LibSpec(_so("data"), ["dkt_augment.hip"], DATA_SIGNATURES, "image datasets have no CPU fallback.", "dkt_abi_data.h", "DKT_DATA_ABI_VERSION",
+                    "dkt_data_abi_version"),
+    "smk": LibSpec(_so("smk"), ["dkt_smk_task.hip"], SMK_SIGNATURES, "there is no CPU fallback.", "dkt_abi_smk.h", "DKT_SMK_ABI_VERSION", "dkt_smk_abi_version"),
+    "diag": LibSpec(_so("diag"), ["dkt_diag.hip", "dkt_mll_reg_twin.hip"], DIAG_SIGNATURES, "the measurement kernels have no fallback.", spill_budget=False),
+}
+LIB_PATH, TWINS_LIB_PATH, X16_LIB_PATH, DATA_LIB_PATH, SMK_LIB_PATH, DIAG_LIB_PATH = (LIBS[k].path for k in ("hip", "twins", "x16", "data", "smk", "diag"))
+
 _lock = threading.Lock()
-_libs = {}          # path -> bound CDLL
+_libs = {}          # path -> bound CDLL; a library that is not in here yet has not had its staleness check in this process either
 
 
 def _lib_path() -> str:
@@ -193,42 +218,51 @@ def check_resources(usage: dict) -> list:
     return bad
 
 
-def _digest(src: str, twins: bool = False) -> str:
-    """Content hash of a source, every header and the flags: the object cache key (mtimes do not survive a checkout)."""
+def _read(path: str) -> bytes:
+    with open(path, "rb") as fh:
+        return fh.read()
+
+
+def _digest(src: str, spec: LibSpec) -> str:
+    """Content hash of a source, the headers it can include (every csrc/*.h and *.inc, include/dkt_abi.h, its library's own ABI header) and the flags: the
+    object cache key (mtimes do not survive a checkout)."""
     import hashlib
+    headers = (sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) +
+               [os.path.join(INCLUDE, f) for f in sorted({"dkt_abi.h", spec.header} - {None})])
     h = hashlib.sha256()
-    extra = [DATA_HEADER] if os.path.basename(src) in DATA_SOURCES else [SMK_HEADER] if os.path.basename(src) in SMK_SOURCES else []
-    for f in [src] + HEADERS + extra:
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    h.update(" ".join(_flags(twins)).encode())
+    for f in [src] + headers:
+        h.update(_read(f))
+    h.update(" ".join(_flags(spec.twins)).encode())
     return h.hexdigest()[:20]
 
 
-def _stamp(sources, replace=None, twins: bool = False) -> str:
-    return ";".join(_digest((replace or {}).get(s, os.path.join(CSRC, s)), twins) for s in sources)
+def _stamp(spec: LibSpec, replace=None) -> str:
+    return ";".join(_digest((replace or {}).get(s, os.path.join(CSRC, s)), spec) for s in spec.sources)
+
+
+def _stale(spec: LibSpec) -> bool:
+    if not os.path.exists(spec.path) or not os.path.exists(spec.path + ".stamp"):
+        return True
+    with open(spec.path + ".stamp") as fh:
+        return fh.read() != _stamp(spec)
 
 
 def needs_build() -> bool:
-    if os.environ.get("DKT_AMD_LIB"):
-        return False
-    if not os.path.exists(LIB_PATH) or not os.path.exists(LIB_PATH + ".stamp"):
-        return True
-    with open(LIB_PATH + ".stamp") as fh:
-        return fh.read() != _stamp(SOURCES)
+    return not os.environ.get("DKT_AMD_LIB") and _stale(LIBS["hip"])
 
 
-def _compile_link(sources, target, replace=None, verbose=False, twins: bool = False, check: bool = True) -> str:
+def _compile_link(spec: LibSpec, target: str = None, replace=None, verbose=False) -> str:
     """One hipcc -c per source (in parallel, objects cached by content hash under build/), then one link."""
     from concurrent.futures import ThreadPoolExecutor
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    sources, target = spec.sources, target or spec.path
     os.makedirs(OBJ_DIR, exist_ok=True)
 
     def one(name):
         src = (replace or {}).get(name, os.path.join(CSRC, name))
-        obj = os.path.join(OBJ_DIR, "%s.%s.o" % (os.path.basename(src), _digest(src, twins)))
+        obj = os.path.join(OBJ_DIR, "%s.%s.o" % (os.path.basename(src), _digest(src, spec)))
         if not os.path.exists(obj) or not os.path.exists(obj + ".res.json"):
-            cmd = [hipcc] + _flags(twins) + ["-c", src, "-o", obj + ".tmp"]
+            cmd = [hipcc] + _flags(spec.twins) + ["-c", src, "-o", obj + ".tmp"]
             if verbose:
                 print(" ".join(cmd))
             res = subprocess.run(cmd, capture_output=True, text=True)
@@ -247,7 +281,7 @@ def _compile_link(sources, target, replace=None, verbose=False, twins: bool = Fa
             usage.update(json.load(fh))
     with open(os.path.join(OBJ_DIR, os.path.basename(target) + ".resource_usage.json"), "w") as fh:
         json.dump(usage, fh, indent=1, sort_keys=True)
-    bad = check_resources(usage) if (check and not twins) else []       # the spill budget is the product library's
+    bad = check_resources(usage) if spec.spill_budget else []
     if bad:
         raise RuntimeError("register spills beyond the budget (deep-kernel-transfer_amd/_lib.py SPILL_BUDGET):\n" +
                            "\n".join("  %s: %d VGPR spills (budget %d)" % b for b in bad))
@@ -257,10 +291,10 @@ def _compile_link(sources, target, replace=None, verbose=False, twins: bool = Fa
         raise RuntimeError("hipcc link failed:\n" + res.stdout + res.stderr)
     os.replace(target + ".tmp", target)
     with open(target + ".stamp", "w") as fh:
-        fh.write(_stamp(sources, replace, twins))
+        fh.write(_stamp(spec, replace))
     if replace is None:
-        # superseded objects of these sources (a header edit re-hashes every file: the cache would otherwise grow by ~ 20 MB per edit); kept: what the three
-        # in-tree libraries were last linked from (this link's objects + whatever the other libraries' lists name)
+        # superseded objects of the in-tree libraries' sources (a header edit re-hashes every file: the cache would otherwise grow by ~ 20 MB per edit); kept:
+        # what each library of LIBS was last linked from (this link's objects + whatever the other libraries' lists name)
         keep_path = os.path.join(OBJ_DIR, os.path.basename(target) + ".objects.json")
         with open(keep_path, "w") as fh:
             json.dump([os.path.basename(o) for o in objs], fh)
@@ -269,9 +303,10 @@ def _compile_link(sources, target, replace=None, verbose=False, twins: bool = Fa
             if f.endswith(".objects.json"):
                 with open(os.path.join(OBJ_DIR, f)) as fh:
                     keep.update(json.load(fh))
+        known = {src for lib in LIBS.values() for src in lib.sources}
         for f in os.listdir(OBJ_DIR):
             base = f[:-len(".res.json")] if f.endswith(".res.json") else f
-            if base.endswith(".o") and base not in keep and any(base.startswith(src + ".") for src in SOURCES + DIAG_SOURCES + X16_SOURCES + DATA_SOURCES + SMK_SOURCES):
+            if base.endswith(".o") and base not in keep and any(base.startswith(src + ".") for src in known):
                 try:
                     os.remove(os.path.join(OBJ_DIR, f))
                 except OSError:
@@ -279,93 +314,68 @@ def _compile_link(sources, target, replace=None, verbose=False, twins: bool = Fa
     return target
 
 
+def _build_if_stale(spec: LibSpec, verbose: bool = False) -> str:
+    return _compile_link(spec, verbose=verbose) if _stale(spec) else spec.path
+
+
 def build(force: bool = False, verbose: bool = False, out: str = None, replace: dict = None) -> str:
-    """hipcc --offload-arch=gfx950 -> deep-kernel-transfer_amd/libdkt_hip.so (in-tree), and libdkt_x16.so brought up to date as well (its own stamp:
-    it is built even when the product library is current).  Cross-compiles without a GPU.  `out` / `replace` ({source name: other path}) build a
-    variant library for A/B runs (the product library only)."""
-    if out is None and not force and not needs_build():
-        build_x16(verbose)
-        build_data(verbose)
-        build_smk(verbose)
-        return LIB_PATH
-    if force and os.path.isdir(OBJ_DIR):
-        for f in os.listdir(OBJ_DIR):
-            if f.endswith(".o"):
-                os.remove(os.path.join(OBJ_DIR, f))
-    path = _compile_link(SOURCES, out or LIB_PATH, replace, verbose)
+    """hipcc --offload-arch=gfx950 -> deep-kernel-transfer_amd/libdkt_hip.so (in-tree), and the other product libraries (x16, data, smk) brought up to date as
+    well (their own stamps: they are built even when the product library is current).  Cross-compiles without a GPU.  `out` / `replace` ({source name: other
+    path}) build a variant library for A/B runs (the product library only)."""
+    path = LIB_PATH
+    if out is not None or force or needs_build():
+        if force and os.path.isdir(OBJ_DIR):
+            for f in os.listdir(OBJ_DIR):
+                if f.endswith(".o"):
+                    os.remove(os.path.join(OBJ_DIR, f))
+        path = _compile_link(LIBS["hip"], out, replace, verbose)
     if out is None:
-        build_x16(verbose)
-        build_data(verbose)
-        build_smk(verbose)
+        for key in ("x16", "data", "smk"):
+            _build_if_stale(LIBS[key], verbose)
     return path
 
 
-def x16_needs_build() -> bool:
-    if not os.path.exists(X16_LIB_PATH) or not os.path.exists(X16_LIB_PATH + ".stamp"):
-        return True
-    with open(X16_LIB_PATH + ".stamp") as fh:
-        return fh.read() != _stamp(X16_SOURCES)
-
-
 def build_x16(verbose: bool = False) -> str:
-    """The 16-bit front-end library libdkt_x16.so (product code: the spill check applies, budget 0)."""
-    if not x16_needs_build():
-        return X16_LIB_PATH
-    return _compile_link(X16_SOURCES, X16_LIB_PATH, None, verbose)
-
-
-def data_needs_build() -> bool:
-    if not os.path.exists(DATA_LIB_PATH) or not os.path.exists(DATA_LIB_PATH + ".stamp"):
-        return True
-    with open(DATA_LIB_PATH + ".stamp") as fh:
-        return fh.read() != _stamp(DATA_SOURCES)
+    return _build_if_stale(LIBS["x16"], verbose)
 
 
 def build_data(verbose: bool = False) -> str:
-    """The episode image-transform library libdkt_data.so (product code: the spill check applies, budget 0)."""
-    if not data_needs_build():
-        return DATA_LIB_PATH
-    return _compile_link(DATA_SOURCES, DATA_LIB_PATH, None, verbose)
-
-
-def smk_needs_build() -> bool:
-    if not os.path.exists(SMK_LIB_PATH) or not os.path.exists(SMK_LIB_PATH + ".stamp"):
-        return True
-    with open(SMK_LIB_PATH + ".stamp") as fh:
-        return fh.read() != _stamp(SMK_SOURCES)
+    return _build_if_stale(LIBS["data"], verbose)
 
 
 def build_smk(verbose: bool = False) -> str:
-    """The task-resident spectral-mixture library libdkt_smk.so (product code: the spill check applies, budget 0)."""
-    if not smk_needs_build():
-        return SMK_LIB_PATH
-    return _compile_link(SMK_SOURCES, SMK_LIB_PATH, None, verbose)
+    return _build_if_stale(LIBS["smk"], verbose)
 
 
 def build_twins(verbose: bool = False) -> str:
-    """The same sources with -DDKT_TWINS (every variant / legacy pipeline / validation twin + the environment switches that select them): libdkt_twins.so,
-    loaded by the tests and the A/B tools only."""
-    if os.path.exists(TWINS_LIB_PATH) and os.path.exists(TWINS_LIB_PATH + ".stamp"):
-        with open(TWINS_LIB_PATH + ".stamp") as fh:
-            if fh.read() == _stamp(SOURCES, None, True):
-                return TWINS_LIB_PATH
-    return _compile_link(SOURCES, TWINS_LIB_PATH, None, verbose, twins=True)
+    return _build_if_stale(LIBS["twins"], verbose)
 
 
 def build_diag(verbose: bool = False) -> str:
-    """The measurement-only kernels (tools/, tests): libdkt_diag.so, never loaded by the product path."""
-    if os.path.exists(DIAG_LIB_PATH) and os.path.exists(DIAG_LIB_PATH + ".stamp"):
-        with open(DIAG_LIB_PATH + ".stamp") as fh:
-            if fh.read() == _stamp(DIAG_SOURCES):
-                return DIAG_LIB_PATH
-    return _compile_link(DIAG_SOURCES, DIAG_LIB_PATH, None, verbose, check=False)
+    return _build_if_stale(LIBS["diag"], verbose)
+
+
+def _header_version(spec: LibSpec) -> int:
+    """The ABI version as the library's header under include/ declares it."""
+    import re
+    with open(os.path.join(INCLUDE, spec.header)) as fh:
+        return int(re.search(r"#define\s+%s\s+(\d+)" % spec.version_macro, fh.read()).group(1))
 
 
 def abi_version_of_header() -> int:
-    """DKT_ABI_VERSION as include/dkt_abi.h declares it."""
-    import re
-    with open(os.path.join(INCLUDE, "dkt_abi.h")) as fh:
-        return int(re.search(r"#define\s+DKT_ABI_VERSION\s+(\d+)", fh.read()).group(1))
+    return _header_version(LIBS["hip"])
+
+
+def x16_abi_version_of_header() -> int:
+    return _header_version(LIBS["x16"])
+
+
+def data_abi_version_of_header() -> int:
+    return _header_version(LIBS["data"])
+
+
+def smk_abi_version_of_header() -> int:
+    return _header_version(LIBS["smk"])
 
 
 def device_code_objects(path: str = None) -> list:
@@ -500,170 +510,65 @@ def unprotected_wide_buffer_stores(path: str = None) -> list:
     return hits
 
 
-def load(path: str = None) -> ctypes.CDLL:
-    """dlopen the HIP library (the product unless `path` / DKT_AMD_LIB says otherwise) and bind every declared symbol; raises (never falls back) on failure."""
-    path = path or _lib_path()
+def _load(spec: LibSpec, path: str = None) -> ctypes.CDLL:
+    """dlopen a library and bind every entry of its signature table; raises (never falls back) when it cannot be built or loaded, lacks a symbol, or implements
+    another ABI version than its header declares.  Without `path`, the library is first brought up to date where the sources are present: once per process (a
+    cached handle returns before that), and inside the lock, so that no thread dlopens a file that another one is replacing.  A `path` is loaded as it is."""
     with _lock:
-        lib = _libs.get(path)
+        lib = _libs.get(path or spec.path)
         if lib is not None:
             return lib
+        if path is None:
+            path = _build_if_stale(spec) if os.path.isdir(CSRC) else spec.path
         if not os.path.exists(path):
-            raise RuntimeError(
-                "%s is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
-                "-- the DKT hot path has no CPU fallback." % path)
+            raise RuntimeError("%s is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` -- %s" % (path, spec.no_fallback))
         lib = ctypes.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in spec.signatures.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:
-                raise RuntimeError("%s lacks symbol %s declared in include/dkt_abi.h" % (os.path.basename(path), name)) from e
+                raise RuntimeError("%s lacks symbol %s declared in %s" % (os.path.basename(path), name, "include/" + spec.header if spec.header else "its signature table")) from e
             fn.restype = res
             fn.argtypes = args
-        want = abi_version_of_header()
-        got = int(lib.dkt_abi_version())
-        if got != want:
-            raise RuntimeError("%s implements DKT_ABI_VERSION %d, include/dkt_abi.h declares %d: rebuild (python -c 'import __graft_entry__ as g; g.build()')"
-                               % (path, got, want))
+        if spec.header is not None:
+            want, got = _header_version(spec), int(getattr(lib, spec.version_symbol)())
+            if got != want:
+                raise RuntimeError("%s implements %s %d, include/%s declares %d: rebuild (python -c 'import __graft_entry__ as g; g.build()')"
+                                   % (path, spec.version_macro, got, spec.header, want))
         _libs[path] = lib
         return lib
 
 
-_twins_checked = False
+def load(path: str = None) -> ctypes.CDLL:
+    """The product library -- or the build of its ABI that `path` / DKT_AMD_LIB names -- as it is: bringing it up to date is build()'s job (one rank's, in a
+    multi-process run)."""
+    return _load(LIBS["hip"], path or _lib_path())
 
 
 def load_twins() -> ctypes.CDLL:
-    """The variant / twin build of the same ABI (tests, A/B tools); built on first use where the sources are present (the staleness check -- a content hash of
-    every source -- runs once per process, not per call)."""
-    global _twins_checked
-    if not _twins_checked:
-        build_twins()
-        _twins_checked = True
-    return load(TWINS_LIB_PATH)
-
-
-_x16_checked = False
-
-
-def x16_abi_version_of_header() -> int:
-    """DKT_X16_ABI_VERSION as include/dkt_abi_x16.h declares it."""
-    import re
-    with open(os.path.join(INCLUDE, "dkt_abi_x16.h")) as fh:
-        return int(re.search(r"#define\s+DKT_X16_ABI_VERSION\s+(\d+)", fh.read()).group(1))
+    return _load(LIBS["twins"])
 
 
 def load_x16() -> ctypes.CDLL:
-    """dlopen libdkt_x16.so and bind every function of include/dkt_abi_x16.h; built on first use where the sources are present (the staleness check runs
-    once per process).  Raises (never falls back) when it cannot be built or loaded."""
-    global _x16_checked
-    if not _x16_checked:
-        if os.path.isdir(CSRC):
-            build_x16()
-        _x16_checked = True
-    path = X16_LIB_PATH
-    with _lock:
-        lib = _libs.get(path)
-        if lib is not None:
-            return lib
-        if not os.path.exists(path):
-            raise RuntimeError("%s is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` -- 16-bit trunk features have no fallback." % path)
-        lib = ctypes.CDLL(path)
-        for name, (res, args) in X16_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise RuntimeError("%s lacks symbol %s declared in include/dkt_abi_x16.h" % (os.path.basename(path), name)) from e
-            fn.restype = res
-            fn.argtypes = args
-        want, got = x16_abi_version_of_header(), int(lib.dkt_x16_abi_version())
-        if got != want:
-            raise RuntimeError("%s implements DKT_X16_ABI_VERSION %d, include/dkt_abi_x16.h declares %d: rebuild" % (path, got, want))
-        _libs[path] = lib
-        return lib
-
-
-_data_checked = False
-
-
-def data_abi_version_of_header() -> int:
-    """DKT_DATA_ABI_VERSION as include/dkt_abi_data.h declares it."""
-    import re
-    with open(DATA_HEADER) as fh:
-        return int(re.search(r"#define\s+DKT_DATA_ABI_VERSION\s+(\d+)", fh.read()).group(1))
+    return _load(LIBS["x16"])
 
 
 def load_data() -> ctypes.CDLL:
-    """dlopen libdkt_data.so and bind every function of include/dkt_abi_data.h; built on first use where the sources are present.  Raises (never
-    falls back) when it cannot be built or loaded."""
-    global _data_checked
-    if not _data_checked:
-        if os.path.isdir(CSRC):
-            build_data()
-        _data_checked = True
-    path = DATA_LIB_PATH
-    with _lock:
-        lib = _libs.get(path)
-        if lib is not None:
-            return lib
-        if not os.path.exists(path):
-            raise RuntimeError("%s is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` -- image datasets have no CPU fallback." % path)
-        lib = ctypes.CDLL(path)
-        for name, (res, args) in DATA_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise RuntimeError("%s lacks symbol %s declared in include/dkt_abi_data.h" % (os.path.basename(path), name)) from e
-            fn.restype = res
-            fn.argtypes = args
-        want, got = data_abi_version_of_header(), int(lib.dkt_data_abi_version())
-        if got != want:
-            raise RuntimeError("%s implements DKT_DATA_ABI_VERSION %d, include/dkt_abi_data.h declares %d: rebuild" % (path, got, want))
-        _libs[path] = lib
-        return lib
-
-
-_smk_checked = False
-
-
-def smk_abi_version_of_header() -> int:
-    """DKT_SMK_ABI_VERSION as include/dkt_abi_smk.h declares it."""
-    import re
-    with open(SMK_HEADER) as fh:
-        return int(re.search(r"#define\s+DKT_SMK_ABI_VERSION\s+(\d+)", fh.read()).group(1))
+    return _load(LIBS["data"])
 
 
 def load_smk() -> ctypes.CDLL:
-    """dlopen libdkt_smk.so and bind every function of include/dkt_abi_smk.h; built on first use where the sources are present.  Raises (never
-    falls back) when it cannot be built or loaded."""
-    global _smk_checked
-    if not _smk_checked:
-        if os.path.isdir(CSRC):
-            build_smk()
-        _smk_checked = True
-    path = SMK_LIB_PATH
-    with _lock:
-        lib = _libs.get(path)
-        if lib is not None:
-            return lib
-        if not os.path.exists(path):
-            raise RuntimeError("%s is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` -- there is no CPU fallback." % path)
-        lib = ctypes.CDLL(path)
-        for name, (res, args) in SMK_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise RuntimeError("%s lacks symbol %s declared in include/dkt_abi_smk.h" % (os.path.basename(path), name)) from e
-            fn.restype = res
-            fn.argtypes = args
-        want, got = smk_abi_version_of_header(), int(lib.dkt_smk_abi_version())
-        if got != want:
-            raise RuntimeError("%s implements DKT_SMK_ABI_VERSION %d, include/dkt_abi_smk.h declares %d: rebuild" % (path, got, want))
-        _libs[path] = lib
-        return lib
+    return _load(LIBS["smk"])
 
 
 def load_diag() -> ctypes.CDLL:
-    """dlopen the measurement-only library (tools / tests); builds it on first use."""
-    return ctypes.CDLL(build_diag())
+    return _load(LIBS["diag"])
+
+
+def reload_env(lib) -> None:
+    """Make a handle re-read its environment switches: through the reload symbol of the spec whose library it is (any other handle is a build of the product ABI)."""
+    spec = next((s for s in LIBS.values() if s.path == lib._name), LIBS["hip"])
+    getattr(lib, spec.reload_symbol)()
 
 
 STATUS = {0: "DKT_OK", -1: "DKT_ERR_BAD_ARG", -2: "DKT_ERR_TOO_LARGE", -3: "DKT_ERR_WORKSPACE", -4: "DKT_ERR_LAUNCH", -5: "DKT_ERR_SHAPE"}

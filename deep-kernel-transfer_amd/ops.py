@@ -151,7 +151,7 @@ def _sync_env(lib, names=None) -> None:
     if seen is None or any(os.environ.get(k) != seen[k] for k in (names or _ENV_SWITCHES)):
         snap = {k: os.environ.get(k) for k in _ENV_SWITCHES}
         if seen is not None or any(v is not None for v in snap.values()):
-            (lib.dkt_x16_reload_env if lib._name == _lib.X16_LIB_PATH else lib.dkt_reload_env)()
+            _lib.reload_env(lib)
         _env_seen[id(lib)] = snap
 
 
@@ -262,9 +262,6 @@ def mll(e: torch.Tensor, y: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor, 
         if per_class or force_generic or force_blocked or force_f32mfma:
             raise RuntimeError("mll: force_reg combines with want_grad / want_chol only")
         dlib = _lib.load_diag()
-        dlib.dkt_diag_mll_reg_f32.restype = ctypes.c_int
-        dlib.dkt_diag_mll_reg_f32.argtypes = ([ctypes.c_void_p] * 2 + [ctypes.c_long] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float, ctypes.c_int, ctypes.c_uint] +
-                                              [ctypes.c_void_p] * 11)
         st = dlib.dkt_diag_mll_reg_f32(_p(e), _p(y), y_bstride, _p(sv), _p(mean), _p(noise), b_, c_, n, float(jitter0), int(max_tries),
                                        flags & (MLL_WANT_GRAD | MLL_WANT_CHOL), _p(cls_weight), _p(logp), _p(alpha), _p(chol), _p(w), _p(dsv), _p(dmean), _p(dnoise),
                                        _p(jit), _p(info), _stream())
