@@ -5,11 +5,13 @@ one-line views of the table.
 There is NO CPU fallback: every entry point of `ops` goes through these libraries, and loading raises if a shared object is missing, lacks a symbol of its
 header or implements another ABI version than the header declares.
 
-Six in-tree shared objects, all hipcc --offload-arch=gfx950:
+Seven in-tree shared objects, all hipcc --offload-arch=gfx950:
   hip    libdkt_hip.so    the PRODUCT (include/dkt_abi.h): the default kernel of every call, no measurement switch, no variant instantiation;
   x16    libdkt_x16.so    product code: the front-end calls for 16-bit (bf16 / f16) trunk features (include/dkt_abi_x16.h); apart so that the product ABI stays as it is;
   data   libdkt_data.so   product code: the episode image transform of the image-dataset loader (include/dkt_abi_data.h); apart for the same reason;
   smk    libdkt_smk.so    product code: the task-resident spectral-mixture kernels of the sine-wave experiment (include/dkt_abi_smk.h); apart for the same reason;
+  gpc    libdkt_gpc.so    product code: Laplace-approximation GP classification at test time, Newton mode finding and prediction (include/dkt_abi_gpc.h); apart for
+                          the same reason;
   twins  libdkt_twins.so  the product's sources with -DDKT_TWINS: every pipeline variant and validation twin the defaults were chosen from, selected by the
                           environment switches of DESIGN.md's appendix.  Same ABI.  Tests and A/B tools only (DKT_TWINS=1 + a variant switch);
   diag   libdkt_diag.so   measurement-only kernels (stream ceilings, co-residency spinners, the round-1 register-sweep kernel): no header, no version.
@@ -112,6 +114,14 @@ SMK_SIGNATURES = {
 }
 SMK_MAX_N, SMK_MAX_M, SMK_MAX_D, SMK_MAX_Q = 32, 256, 64, 8      # the limits of include/dkt_abi_smk.h (DKT_ERR_SHAPE outside them)
 
+# libdkt_gpc.so (include/dkt_abi_gpc.h; tests check that this lists every function of the header)
+GPC_SIGNATURES = {
+    "dkt_gpc_abi_version": (_c_i, []),
+    "dkt_gpc_mode_f32": (_c_i, [_c_p, ctypes.c_long, ctypes.c_long, _c_p, ctypes.c_long] + [_c_p] * 6 + [_c_i, _c_i, _c_i, _c_i, _c_p]),
+    "dkt_gpc_predict_f32": (_c_i, [_c_p, ctypes.c_long, ctypes.c_long, _c_p, ctypes.c_long, ctypes.c_long] + [_c_p] * 7 + [_c_i, _c_i, _c_i, _c_i, _c_p]),
+}
+GPC_MAX_N, GPC_MAX_C = 127, 32      # the limits of include/dkt_abi_gpc.h (DKT_ERR_SHAPE outside them)
+
 # libdkt_diag.so has no header: the entries below are bound at load, and callers of its other exports (tools, tests) set their own argtypes on the handle
 DIAG_SIGNATURES = {
     "dkt_diag_mll_reg_f32": (_c_i, [_c_p, _c_p, ctypes.c_long, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_f, _c_i, ctypes.c_uint] + [_c_p] * 11),
@@ -146,9 +156,11 @@ LIBS = {
     "data": LibSpec(_so("data"), ["dkt_augment.hip"], DATA_SIGNATURES, "image datasets have no CPU fallback.", "dkt_abi_data.h", "DKT_DATA_ABI_VERSION",
                     "dkt_data_abi_version"),
     "smk": LibSpec(_so("smk"), ["dkt_smk_task.hip"], SMK_SIGNATURES, "there is no CPU fallback.", "dkt_abi_smk.h", "DKT_SMK_ABI_VERSION", "dkt_smk_abi_version"),
+    "gpc": LibSpec(_so("gpc"), ["dkt_gpc.hip"], GPC_SIGNATURES, "Laplace GP classification on the device has no fallback.", "dkt_abi_gpc.h", "DKT_GPC_ABI_VERSION",
+                   "dkt_gpc_abi_version"),
     "diag": LibSpec(_so("diag"), ["dkt_diag.hip", "dkt_mll_reg_twin.hip"], DIAG_SIGNATURES, "the measurement kernels have no fallback.", spill_budget=False),
 }
-LIB_PATH, TWINS_LIB_PATH, X16_LIB_PATH, DATA_LIB_PATH, SMK_LIB_PATH, DIAG_LIB_PATH = (LIBS[k].path for k in ("hip", "twins", "x16", "data", "smk", "diag"))
+LIB_PATH, TWINS_LIB_PATH, X16_LIB_PATH, DATA_LIB_PATH, SMK_LIB_PATH, GPC_LIB_PATH, DIAG_LIB_PATH = (LIBS[k].path for k in ("hip", "twins", "x16", "data", "smk", "gpc", "diag"))
 
 _lock = threading.Lock()
 _libs = {}          # path -> bound CDLL; a library that is not in here yet has not had its staleness check in this process either
@@ -319,7 +331,7 @@ def _build_if_stale(spec: LibSpec, verbose: bool = False) -> str:
 
 
 def build(force: bool = False, verbose: bool = False, out: str = None, replace: dict = None) -> str:
-    """hipcc --offload-arch=gfx950 -> deep-kernel-transfer_amd/libdkt_hip.so (in-tree), and the other product libraries (x16, data, smk) brought up to date as
+    """hipcc --offload-arch=gfx950 -> deep-kernel-transfer_amd/libdkt_hip.so (in-tree), and the other product libraries (x16, data, smk, gpc) brought up to date as
     well (their own stamps: they are built even when the product library is current).  Cross-compiles without a GPU.  `out` / `replace` ({source name: other
     path}) build a variant library for A/B runs (the product library only)."""
     path = LIB_PATH
@@ -330,7 +342,7 @@ def build(force: bool = False, verbose: bool = False, out: str = None, replace: 
                     os.remove(os.path.join(OBJ_DIR, f))
         path = _compile_link(LIBS["hip"], out, replace, verbose)
     if out is None:
-        for key in ("x16", "data", "smk"):
+        for key in ("x16", "data", "smk", "gpc"):
             _build_if_stale(LIBS[key], verbose)
     return path
 
@@ -345,6 +357,10 @@ def build_data(verbose: bool = False) -> str:
 
 def build_smk(verbose: bool = False) -> str:
     return _build_if_stale(LIBS["smk"], verbose)
+
+
+def build_gpc(verbose: bool = False) -> str:
+    return _build_if_stale(LIBS["gpc"], verbose)
 
 
 def build_twins(verbose: bool = False) -> str:
@@ -376,6 +392,10 @@ def data_abi_version_of_header() -> int:
 
 def smk_abi_version_of_header() -> int:
     return _header_version(LIBS["smk"])
+
+
+def gpc_abi_version_of_header() -> int:
+    return _header_version(LIBS["gpc"])
 
 
 def device_code_objects(path: str = None) -> list:
@@ -559,6 +579,10 @@ def load_data() -> ctypes.CDLL:
 
 def load_smk() -> ctypes.CDLL:
     return _load(LIBS["smk"])
+
+
+def load_gpc() -> ctypes.CDLL:
+    return _load(LIBS["gpc"])
 
 
 def load_diag() -> ctypes.CDLL:

@@ -6,6 +6,8 @@
     .train_loop(epoch, loader, optimizer)    train.py:50     (optimizer ignored, Adam re-created: DKT.py:114)
     .test_loop(loader, record=None, return_std=False)        train.py:56, test.py:161
     .correct(x, N=0, laplace=False) -> (top1_correct, count, avg_loss)       DKT.py:199-272
+        laplace=True: Laplace-approximation GP classification with 1.0 * RBF(0.1), on the device up to 127 support rows (docs/LAPLACE.md);
+        laplace="deep": the same with the model's own trained kernel; .laplace_proba(x, kernel) their class probabilities; .laplace the default of test_loop
     .get_logits(x) -> [n_way*n_query, n_way]                 test_uncertainty.py:197
     .set_forward / .set_forward_loss         stubs (DKT.py:73-77)
     .feature / .feature_extractor / .model / .likelihood / .mll / .normalize / .iteration / .writer
@@ -198,6 +200,7 @@ class DKT(MetaTemplate):
         self._target_cache = {}
         self._grad_bucket = None
         self._last = {}
+        self.laplace = False      # what test_loop passes to _correct_device: False (the paper's method), True or "deep" (docs/LAPLACE.md)
 
     @property
     def amp(self):
@@ -672,6 +675,65 @@ class DKT(MetaTemplate):
         x_query = xd[:, self.n_support:].contiguous().view(self.n_way * self.n_query, *xd.size()[2:])
         return x_support, x_query
 
+    # ---- Laplace-approximation GP classification on the device (libdkt_gpc.so; docs/LAPLACE.md) ----
+    def _laplace_targets(self, n_way, per_class, device):
+        """{0,1} one-vs-rest targets [C, N]; two classes: ONE binary problem with class 1 positive, as sklearn fits it."""
+        key = ("laplace", n_way, per_class, str(device))
+        y = self._target_cache.get(key)
+        if y is None:
+            y = ((self._targets(n_way, per_class, device) + 1.0) * 0.5)[1 if n_way == 2 else 0:].contiguous()
+            self._target_cache[key] = y
+        return y
+
+    def _laplace_kernels(self, zs, zq, kernel):
+        """K, Ks, kss of episodes zs [B,N,D] (support), zq [B,M,D] (queries): "rbf0.1" = the reference's 1.0 * RBF(0.1), shared by the classes;
+        "deep" = the model's own kernel outputscale_c * E_c, per class."""
+        if kernel == "rbf0.1":
+            ls = torch.full((1,), 0.1, device=zs.device, dtype=torch.float32)
+            return (ops.gram(zs, None, ops.KERNEL_RBF, ls), ops.gram(zq, zs, ops.KERNEL_RBF, ls),
+                    torch.ones(zq.shape[:2], device=zs.device, dtype=torch.float32))
+        if kernel != "deep":
+            raise ValueError("laplace kernel must be 'rbf0.1' or 'deep', got %r" % (kernel,))
+        pick = slice(1, 2) if self.n_way == 2 else slice(None)
+        sv = self._hypers()[0].detach()[pick]
+        if self.kernel_type in LINEAR_KINDS:
+            e, ex = ops.kernel_matrix(zs, None, self.kernel_type).unsqueeze(1), ops.kernel_matrix(zq, zs, self.kernel_type).unsqueeze(1)
+            exx = (zq * zq).sum(-1).unsqueeze(1)
+        else:
+            ls, off = self.model.lengthscale, self.model.offset
+            ls, off = (None if ls is None else ls.detach()), (None if off is None else off.detach())
+            e = ops.kernel_matrix_per_class(zs, None, self.kernel_type, ls, off)[:, pick]
+            ex = ops.kernel_matrix_per_class(zq, zs, self.kernel_type, ls, off)[:, pick]
+            exx = torch.diagonal(ops.kernel_matrix_per_class(zq, None, self.kernel_type, ls, off)[:, pick], dim1=-2, dim2=-1)
+        return sv.view(1, -1, 1, 1) * e, sv.view(1, -1, 1, 1) * ex, (sv.view(1, -1, 1) * exx).contiguous()
+
+    def _laplace_device(self, x, kernel, batched=False):
+        """An episode x [n_way, n_support + n_query, ...] (batched: B of them, [B, n_way, ...]) -> (mu, var, prob [B,C,M], labels [B,M]): one backbone
+        pass per episode (so that a batch reproduces its episodes' own results bit for bit, whatever the convolutions do with another batch size), the kernel
+        matrices, then ONE mode launch and ONE predict launch for all B x C binary problems."""
+        self._check_way(self.n_way)
+        xd = self._upload(x if batched else x.unsqueeze(0))
+        b_, ns, nq = xd.shape[0], self.n_way * self.n_support, self.n_way * (xd.shape[2] - self.n_support)
+        if not ops.laplace_supported(ns, self.n_way):
+            raise RuntimeError("Laplace GPC on the device takes up to %d support rows and %d classes, the episode has %d and %d"
+                               % (ops._lib.GPC_MAX_N, ops._lib.GPC_MAX_C, ns, self.n_way))
+        with torch.no_grad():
+            z = torch.stack([self._embed(torch.cat([xe[:, :self.n_support].reshape(ns, *xe.shape[2:]), xe[:, self.n_support:].reshape(nq, *xe.shape[2:])], 0))
+                             for xe in xd], 0).detach().float()
+            zs, zq = z[:, :ns].contiguous(), z[:, ns:].contiguous()
+            k, ks, kss = self._laplace_kernels(zs, zq, kernel)
+            mode = ops.laplace_mode(k, self._laplace_targets(self.n_way, self.n_support, z.device))
+            self._last["laplace_mode"] = mode
+            return ops.laplace_predict(ks, kss, mode)
+
+    def laplace_proba(self, x, kernel="rbf0.1", batched=False):
+        """Class probabilities of the Laplace GP classifier, [n_way * n_query, n_way] (batched: x is [B, n_way, ...] and the result [B, n_way * n_query,
+        n_way], from one pair of launches), rows normalised to sum 1 as sklearn's multi-class `predict_proba` does; kernel "rbf0.1" (the reference's
+        1.0 * RBF(0.1)) or "deep" (the model's own trained kernel)."""
+        prob = self._laplace_device(x, kernel, batched)[2].transpose(1, 2)
+        prob = torch.cat([1.0 - prob, prob], 2) if self.n_way == 2 else prob / prob.sum(2, keepdim=True)
+        return prob.contiguous() if batched else prob[0].contiguous()
+
     def correct(self, x, N=0, laplace=False):
         out = self._correct_device(x, N, laplace)
         if not isinstance(out[0], torch.Tensor):
@@ -685,10 +747,15 @@ class DKT(MetaTemplate):
     def _correct_device(self, x, N=0, laplace=False):
         """`correct` without the read-back: returns (stats, count, avg_loss) with stats = [top1_correct, max |info|] on the device."""
         self._check_way(self.n_way)
+        if laplace and (laplace == "deep" or ops.laplace_supported(self.n_way * self.n_support, self.n_way)):
+            # Laplace GPC on the device: 1.0 * RBF(0.1) as the reference fits it, or the model's own kernel; top1 counted on the device
+            labels = self._laplace_device(x, "deep" if laplace == "deep" else "rbf0.1")[3][0]
+            y_q = torch.arange(self.n_way, device=labels.device, dtype=torch.int32).repeat_interleave(self.n_query)
+            return torch.stack([(labels == y_q).sum().float(), torch.zeros((), device=labels.device)]), self.n_way * self.n_query, 0.0
         x_support, x_query = self._split(x)
         y_query = np.repeat(range(self.n_way), self.n_query)
 
-        if laplace:   # sklearn Laplace GPC, "not the method used in the paper" (DKT.py:207-222)
+        if laplace:   # more than 127 support rows: sklearn Laplace GPC, "not the method used in the paper" (DKT.py:207-222)
             from sklearn.gaussian_process import GaussianProcessClassifier
             from sklearn.gaussian_process.kernels import RBF
             y_support = np.repeat(range(self.n_way), self.n_support)
@@ -745,7 +812,9 @@ class DKT(MetaTemplate):
             if self.change_way:
                 self.n_way = x.size(0)
             # the per-episode counts stay on the device and are read back in one go at the print points: no blocking call per episode
-            stats, count_this, loss_value = self._correct_device(x)
+            stats, count_this, loss_value = self._correct_device(x, 0, self.laplace)
+            if not isinstance(stats, torch.Tensor):               # the sklearn route (Laplace, more than 127 support rows) counts on the host
+                stats = torch.tensor([stats, 0.0], device=self.device)
             pending.append((stats, count_this))
             if i % 100 == 0 or i == iter_num - 1:
                 got = torch.stack([p[0] for p in pending]).cpu().numpy()

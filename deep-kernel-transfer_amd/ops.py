@@ -611,6 +611,60 @@ def smk_any(x1: torch.Tensor, x2: Optional[torch.Tensor], weights: torch.Tensor,
 CLASSMAP_RBF, CLASSMAP_MATERN25, CLASSMAP_POLY = 0, 1, 2
 
 
+# Laplace-approximation GP classification (libdkt_gpc.so, include/dkt_abi_gpc.h): no autograd
+def laplace_supported(n: int, c: int) -> bool:
+    """Whether dkt_gpc_mode_f32 / dkt_gpc_predict_f32 take N support rows and C binary problems per episode."""
+    return 1 <= n <= _lib.GPC_MAX_N and 1 <= c <= _lib.GPC_MAX_C
+
+
+def laplace_mode(K: torch.Tensor, Y: torch.Tensor, max_iter: int = 100) -> dict:
+    """Posterior modes of B x C binary Laplace GPC problems in ONE launch (scikit-learn's `_posterior_mode`, the Newton loop inside the kernel).
+    K: [B,N,N] (shared by the C problems of an episode) or [B,C,N,N]; Y: targets in {0,1}, [C,N] (every episode) or [B,C,N].
+    Returns dict(f [B,C,N], g = y - pi [B,C,N], w_sr = W^1/2 [B,C,N], chol = L [B,C,N,N], lml [B,C], iters [B,C] int32): g, w_sr, chol are those of
+    the last executed iteration and S = W^1/2 B^-1 W^1/2 = (L^-1 diag(w_sr))^T (L^-1 diag(w_sr)); `laplace_predict` solves with L instead of forming S."""
+    per_class = K.dim() == 4
+    K = _req(K, "K", 4 if per_class else 3)
+    Y = _req(Y, "Y", Y.dim() if Y.dim() in (2, 3) else 2)
+    b_, n = K.shape[0], K.shape[-1]
+    c_ = Y.shape[-2]
+    if K.shape[-2] != n or Y.shape[-1] != n or (per_class and K.shape[1] != c_) or (Y.dim() == 3 and Y.shape[0] != b_):
+        raise RuntimeError("laplace_mode: K must be [B,N,N] or [B,C,N,N] and Y [C,N] or [B,C,N], got %s and %s" % (tuple(K.shape), tuple(Y.shape)))
+    dev = K.device
+    out = dict(f=torch.empty((b_, c_, n), device=dev, dtype=torch.float32), g=torch.empty((b_, c_, n), device=dev, dtype=torch.float32),
+               w_sr=torch.empty((b_, c_, n), device=dev, dtype=torch.float32), chol=torch.empty((b_, c_, n, n), device=dev, dtype=torch.float32),
+               lml=torch.empty((b_, c_), device=dev, dtype=torch.float32), iters=torch.empty((b_, c_), device=dev, dtype=torch.int32))
+    with _timed("dkt_gpc_mode_f32"):
+        st = _lib.load_gpc().dkt_gpc_mode_f32(_p(K), (c_ if per_class else 1) * n * n, n * n if per_class else 0, _p(Y), c_ * n if Y.dim() == 3 else 0,
+                                              _p(out["f"]), _p(out["g"]), _p(out["w_sr"]), _p(out["chol"]), _p(out["lml"]), _p(out["iters"]),
+                                              b_, c_, n, int(max_iter), _stream())
+    _lib.check(st, "dkt_gpc_mode_f32")
+    return out
+
+
+def laplace_predict(Ks: torch.Tensor, kss: torch.Tensor, mode: dict):
+    """Latent mean and variance, class probability and one-vs-rest label at M query points, ONE launch (scikit-learn's binary `predict_proba` per
+    class and `OneVsRestClassifier.predict`).  Ks: cross kernel [B,M,N] or [B,C,M,N]; kss: prior variance of the queries [B,M] or [B,C,M]; mode: of
+    `laplace_mode`.  Returns (mu, var, prob [B,C,M], labels [B,M] int32: the LAST of several equal maxima of prob; C == 1: mu > 0)."""
+    ks_pc, kss_pc = Ks.dim() == 4, kss.dim() == 3
+    Ks = _req(Ks, "Ks", 4 if ks_pc else 3)
+    kss = _req(kss, "kss", 3 if kss_pc else 2)
+    g, w_sr, chol = _req(mode["g"], "mode['g']", 3), _req(mode["w_sr"], "mode['w_sr']", 3), _req(mode["chol"], "mode['chol']", 4)
+    b_, c_, n = g.shape
+    m = Ks.shape[-2]
+    if (Ks.shape[0] != b_ or Ks.shape[-1] != n or (ks_pc and Ks.shape[1] != c_) or kss.shape[0] != b_ or kss.shape[-1] != m or (kss_pc and kss.shape[1] != c_)
+            or tuple(w_sr.shape) != (b_, c_, n) or tuple(chol.shape) != (b_, c_, n, n)):
+        raise RuntimeError("laplace_predict: Ks %s / kss %s do not fit a mode of B=%d, C=%d, N=%d" % (tuple(Ks.shape), tuple(kss.shape), b_, c_, n))
+    dev = Ks.device
+    mu, var, prob = (torch.empty((b_, c_, m), device=dev, dtype=torch.float32) for _ in range(3))
+    labels = torch.empty((b_, m), device=dev, dtype=torch.int32)
+    with _timed("dkt_gpc_predict_f32"):
+        st = _lib.load_gpc().dkt_gpc_predict_f32(_p(Ks), (c_ if ks_pc else 1) * m * n, m * n if ks_pc else 0, _p(kss), (c_ if kss_pc else 1) * m,
+                                                 m if kss_pc else 0, _p(g), _p(w_sr), _p(chol), _p(mu), _p(var), _p(prob), _p(labels), b_, c_, m, n,
+                                                 _stream())
+    _lib.check(st, "dkt_gpc_predict_f32")
+    return mu, var, prob, labels
+
+
 def _classmap_of(kernel: str, lengthscale, offset):
     """(map id, power, parameter [C], base-matrix kind) of a kernel whose class models own their base-kernel parameter."""
     if kernel in POLY_KINDS:
