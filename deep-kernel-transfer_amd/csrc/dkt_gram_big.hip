@@ -499,15 +499,23 @@ template <int KS>
 void launch_rows(const float* W, const float* Z, float* dZ, int B, int N, int D, const float* sc, hipStream_t st) {
     // 128-row blocks: N > 256 always (three or more blocks per episode); 128 < N <= 256 when the slab loop is long enough to pay for the larger prologue (D >= 128:
     // 0.34 vs 0.41 ms at N = 256, 0.21 vs 0.23 at N = 190, D = 512; at D = 64 the 64-row kernel wins, 0.11 vs 0.125 ms) and the batch fills the GPU with them
-    if (gram_bwd_rows8_enabled() && (KS >= 10 || (D >= 128 && (long)B * ((N + 127) / 128) >= 256))) {
+    // (the product has no DKT_GRAM_BWD_ROWS8 switch: N > 256 never reaches the 64-row kernel there, and its KS >= 10 instances exist in the twins library only)
+#ifdef DKT_TWINS
+    constexpr bool kRows4 = true;
+#else
+    constexpr bool kRows4 = KS < 10;
+#endif
+    if (!kRows4 || (gram_bwd_rows8_enabled() && (KS >= 10 || (D >= 128 && (long)B * ((N + 127) / 128) >= 256)))) {
         const int nrb = (N + 127) / 128;
         const int grid = 8 * ((B + 7) / 8) * nrb;
         hipLaunchKernelGGL((gram_bwd_rows_f16x2_kernel<KS, 8>), dim3(grid), dim3(512), dkt_lds_pad("DKT_PAD_GRAM_BIG_BWD"), st, W, Z, dZ, B, N, D, sc, nrb);
         return;
     }
-    const int nrb = (N + 63) / 64;
-    const int grid = 8 * ((B + 7) / 8) * nrb;
-    hipLaunchKernelGGL((gram_bwd_rows_f16x2_kernel<KS, 4>), dim3(grid), dim3(256), dkt_lds_pad("DKT_PAD_GRAM_BIG_BWD"), st, W, Z, dZ, B, N, D, sc, nrb);
+    if constexpr (kRows4) {
+        const int nrb = (N + 63) / 64;
+        const int grid = 8 * ((B + 7) / 8) * nrb;
+        hipLaunchKernelGGL((gram_bwd_rows_f16x2_kernel<KS, 4>), dim3(grid), dim3(256), dkt_lds_pad("DKT_PAD_GRAM_BIG_BWD"), st, W, Z, dZ, B, N, D, sc, nrb);
+    }
 }
 
 }  // namespace

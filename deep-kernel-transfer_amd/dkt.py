@@ -128,6 +128,9 @@ class _MetaBatched:
                 xs, ys = [], []
 
 
+LIKELIHOODS = ("gaussian", "bernoulli")
+
+
 class _GraphedTrainStep:
     """One training step (backbone forward / backward, the GP hot path, Adam) captured into a hipGraph (torch.cuda.CUDAGraph):
     three eager warm-up steps on a side stream -- they are real steps on real episodes --, then capture, then one graph launch
@@ -173,8 +176,13 @@ class _GraphedTrainStep:
 
 
 class DKT(MetaTemplate):
-    def __init__(self, model_func, n_way, n_support, kernel_type=None, amp=None):
+    def __init__(self, model_func, n_way, n_support, kernel_type=None, amp=None, likelihood="gaussian"):
         super(DKT, self).__init__(model_func, n_way, n_support)
+        if likelihood not in LIKELIHOODS:
+            raise ValueError("likelihood must be one of %s, got %r" % (LIKELIHOODS, likelihood))
+        # "gaussian": regression on +-1 labels (the paper's method, the reference's only objective); "bernoulli": the Laplace approximation of the log marginal
+        # likelihood under a Bernoulli likelihood (docs/LAPLACE.md "Training"; up to 127 rows per episode).  Not a module, parameter or buffer: the state dict is the same
+        self.likelihood_type = likelihood
         self.kernel_type = configs.kernel_type if kernel_type is None else kernel_type
         # mixed-precision backbone (opt-in): "bf16" runs the backbone under torch.autocast up to, not including, bn_out; the GP head stays fp32.
         # The fused front end takes the 16-bit trunk features as they are (libdkt_x16.so); every other route converts them once with .float().
@@ -200,7 +208,9 @@ class DKT(MetaTemplate):
         self._target_cache = {}
         self._grad_bucket = None
         self._last = {}
-        self.laplace = False      # what test_loop passes to _correct_device: False (the paper's method), True or "deep" (docs/LAPLACE.md)
+        # what test_loop passes to _correct_device: False (the paper's method), True or "deep" (docs/LAPLACE.md); a model trained under the Bernoulli likelihood
+        # predicts with it
+        self.laplace = "deep" if self.likelihood_type == "bernoulli" else False
 
     @property
     def amp(self):
@@ -263,6 +273,19 @@ class DKT(MetaTemplate):
             self._target_cache[key] = y
         return y
 
+    @staticmethod
+    def _check_bernoulli_rows(n, c=1):
+        if c > ops._lib.LAPLACE_MAX_C:
+            raise ValueError("likelihood='bernoulli' takes up to %d classes, the episode has %d" % (ops._lib.LAPLACE_MAX_C, c))
+        if n > ops._lib.LAPLACE_MAX_N:
+            raise ValueError("likelihood='bernoulli' takes episodes of up to %d rows (n_way * (n_support + n_query)), this one has %d"
+                             % (ops._lib.LAPLACE_MAX_N, n))
+
+    @staticmethod
+    def _bernoulli_targets(y):
+        """The {0,1} form of the +-1 one-vs-rest targets."""
+        return ((y + 1.0) * 0.5).contiguous()
+
     def _check_way(self, n_way):
         if n_way != self.model.n_models:
             raise RuntimeError("DKT was built with %d GP models but the episode has %d classes "
@@ -320,13 +343,20 @@ class DKT(MetaTemplate):
         sv, mean, noise = self._hypers()
         cw = torch.full((c,), -1.0 / (c * n), device=xb.device, dtype=torch.float32)
         bn = getattr(self.feature_extractor.trunk, "bn_out", None) if self.kernel_type == "bncossim" else None
-        if bn is not None:
-            outs = ops.episode_loss_bn(xb, bn.weight, bn.bias, y, sv, mean, noise, cw, eps=bn.eps, jitter0=self.jitter0,
-                                       max_tries=self.max_tries, use_bn=True, full=True)
+        if self.likelihood_type == "bernoulli":
+            self._check_bernoulli_rows(n, c)
+            obj, logp, iters, e, bmean, bvar, a, s, rnorm = ops.episode_loss_laplace_bn(
+                xb, None if bn is None else bn.weight, None if bn is None else bn.bias, self._bernoulli_targets(y), sv, cw,
+                eps=1e-5 if bn is None else bn.eps, use_bn=bn is not None)
+            alpha, jit, info = None, None, torch.zeros_like(iters)      # (B = I + W^1/2 K W^1/2 has eigenvalues >= 1: no jitter ladder, nothing can fail)
         else:
-            outs = ops.episode_loss_bn(xb, None, None, y, sv, mean, noise, cw, jitter0=self.jitter0, max_tries=self.max_tries,
-                                       use_bn=False, full=True)
-        obj, logp, alpha, info, jit, e, bmean, bvar, a, s, rnorm = outs
+            if bn is not None:
+                outs = ops.episode_loss_bn(xb, bn.weight, bn.bias, y, sv, mean, noise, cw, eps=bn.eps, jitter0=self.jitter0,
+                                           max_tries=self.max_tries, use_bn=True, full=True)
+            else:
+                outs = ops.episode_loss_bn(xb, None, None, y, sv, mean, noise, cw, jitter0=self.jitter0, max_tries=self.max_tries,
+                                           use_bn=False, full=True)
+            obj, logp, alpha, info, jit, e, bmean, bvar, a, s, rnorm = outs
         with torch.no_grad():
             if bn is not None and bn.track_running_stats:
                 mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked.item() + 1)
@@ -360,6 +390,14 @@ class DKT(MetaTemplate):
         c = y.shape[-2]
         sv, mean, noise = self._hypers()
         cw = torch.full((c,), -1.0 / (c * n), device=zb.device, dtype=torch.float32)
+        if self.likelihood_type == "bernoulli":
+            # minimise -(1/C) sum_c lml_c / N of the Laplace approximation (the reference's SumMarginalLogLikelihood / ExactMarginalLogLikelihood scaling,
+            # DKT.py:160-163); the Gaussian noise and the constant mean do not enter this model and receive no gradient
+            self._check_bernoulli_rows(n, c)
+            obj, logp, iters, e = ops.episode_loss_laplace(zb, self._bernoulli_targets(y), sv, cw, self.kernel_type, self.model.lengthscale, self.model.offset,
+                                                           unit_rows=bool(self.normalize))
+            aux = dict(logp=logp, alpha=None, info=torch.zeros_like(iters), jitter=None, e=e.detach(), iters=iters)
+            return obj.mean(), aux
         if self.kernel_type in LINEAR_KINDS:
             obj, logp, alpha, info, jit, e = ops.episode_loss_linear(zb, y, sv, mean, noise, cw, self.jitter0, self.max_tries,
                                                                      unit_rows=bool(self.normalize))
@@ -619,6 +657,8 @@ class DKT(MetaTemplate):
             if self.writer is not None:
                 self.writer.add_scalar('loss', loss, self.iteration)
 
+            # (likelihood="bernoulli": this in-loop evaluation, and the Noise it prints, are still the Gaussian posterior's on the +-1 targets -- a cheap
+            #  progress indicator with the trained kernel, not the Laplace predictor test_loop uses; docs/LAPLACE.md "Training")
             # evaluation on support / query with eval-mode features, conditioning on the (stale)
             # train-mode features and the post-step hyper-parameters (DKT.py:170-192).  Its only consumers are the TensorBoard
             # writer and the log line, and it has no side effect (eval-mode BatchNorm), so it runs only when one of them will
@@ -744,14 +784,40 @@ class DKT(MetaTemplate):
             raise RuntimeError("DKT.correct: kernel matrix not positive definite after jitter retries")
         return float(stats[0].item()), count_this, avg_loss
 
+    def _adapt_bernoulli(self, x, N):
+        """N Adam steps on the GP hyper-parameters under the Laplace objective of the support set; returns the mean loss."""
+        x_support, _ = self._split(x)
+        y_targets = self._targets(self.n_way, self.n_support, self.device)
+        z_train = self._embed(x_support).detach()
+        self.model.train()
+        self.likelihood.train()
+        self.feature_extractor.eval()
+        optimizer = torch.optim.Adam([{'params': self.model.parameters()}], lr=1e-3)
+        total = 0.0
+        for _ in range(N):
+            optimizer.zero_grad()
+            loss, _ = self._episode_loss(z_train, y_targets)
+            loss.backward()
+            optimizer.step()
+            total = total + loss.item()
+        self.model.eval()
+        self.likelihood.eval()
+        return total / float(N + 1e-10)
+
     def _correct_device(self, x, N=0, laplace=False):
         """`correct` without the read-back: returns (stats, count, avg_loss) with stats = [top1_correct, max |info|] on the device."""
         self._check_way(self.n_way)
+        avg_loss = 0.0
+        if self.likelihood_type == "bernoulli":
+            # a model trained under the Bernoulli likelihood adapts (N > 0: the GP hyper-parameters only, DKT.py:242-256) and predicts under it
+            laplace = laplace or "deep"
+            if N > 0:
+                avg_loss = self._adapt_bernoulli(x, N)
         if laplace and (laplace == "deep" or ops.laplace_supported(self.n_way * self.n_support, self.n_way)):
             # Laplace GPC on the device: 1.0 * RBF(0.1) as the reference fits it, or the model's own kernel; top1 counted on the device
             labels = self._laplace_device(x, "deep" if laplace == "deep" else "rbf0.1")[3][0]
             y_q = torch.arange(self.n_way, device=labels.device, dtype=torch.int32).repeat_interleave(self.n_query)
-            return torch.stack([(labels == y_q).sum().float(), torch.zeros((), device=labels.device)]), self.n_way * self.n_query, 0.0
+            return torch.stack([(labels == y_q).sum().float(), torch.zeros((), device=labels.device)]), self.n_way * self.n_query, avg_loss
         x_support, x_query = self._split(x)
         y_query = np.repeat(range(self.n_way), self.n_query)
 

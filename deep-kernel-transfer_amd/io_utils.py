@@ -41,6 +41,8 @@ def parse_args(script, argv=None):
     parser.add_argument('--image_size', default=None, type=int, help='override the backbone-dependent image size')
     parser.add_argument('--n_episode', default=None, type=int, help='episodes per epoch (train: 100) / per test run (600)')
     parser.add_argument('--meta_batch', default=1, type=int, help='[train, this build] episodes per Adam step through the batched hot path (1 = the reference: one step per episode)')
+    parser.add_argument('--likelihood', default='gaussian', choices=['gaussian', 'bernoulli'],
+                        help='[this build] gaussian: regression on +-1 labels (the reference); bernoulli: the Laplace marginal likelihood of a GP classifier, episodes of up to 127 rows (default: gaussian)')
     _add_amp(parser)
     if script == 'train':
         parser.add_argument('--num_classes', default=200, type=int, help='(baseline only; kept for CLI compatibility)')
@@ -126,6 +128,8 @@ def checkpoint_dir_for(params, save_dir):
     if params.train_aug:
         d += '_aug'
     d += '_%dway_%dshot' % (params.train_n_way, params.n_shot)
+    if getattr(params, 'likelihood', 'gaussian') == 'bernoulli':         # (the Gaussian default keeps the reference's directory name)
+        d += '_bernoulli'
     return d
 
 

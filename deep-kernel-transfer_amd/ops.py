@@ -611,7 +611,8 @@ def smk_any(x1: torch.Tensor, x2: Optional[torch.Tensor], weights: torch.Tensor,
 CLASSMAP_RBF, CLASSMAP_MATERN25, CLASSMAP_POLY = 0, 1, 2
 
 
-# Laplace-approximation GP classification (libdkt_gpc.so, include/dkt_abi_gpc.h): no autograd
+# Laplace-approximation GP classification: mode finding and prediction (libdkt_gpc.so, include/dkt_abi_gpc.h) have no autograd; training goes through
+# `laplace_objective` below (dkt_laplace_grad_f32 of the product library: the gradient of the approximate log marginal likelihood at the mode)
 def laplace_supported(n: int, c: int) -> bool:
     """Whether dkt_gpc_mode_f32 / dkt_gpc_predict_f32 take N support rows and C binary problems per episode."""
     return 1 <= n <= _lib.GPC_MAX_N and 1 <= c <= _lib.GPC_MAX_C
@@ -663,6 +664,145 @@ def laplace_predict(Ks: torch.Tensor, kss: torch.Tensor, mode: dict):
                                                  _stream())
     _lib.check(st, "dkt_gpc_predict_f32")
     return mu, var, prob, labels
+
+
+def laplace_grad(K: torch.Tensor, Y: torch.Tensor, f_hat: torch.Tensor, cls_weight: Optional[torch.Tensor], scale: Optional[torch.Tensor] = None):
+    """Laplace log marginal likelihood at the mode f_hat and its gradient (dkt_laplace_grad_f32; docs/LAPLACE.md "Training").  K: [B,N,N] (shared by the
+    C problems of an episode) or [B,C,N,N]; the covariance of problem (b, c) is scale[c] * K; Y in {0,1}: [C,N] or [B,C,N]; f_hat [B,C,N] of
+    `laplace_mode` on those covariances.  Returns (lml [B,C] unweighted, dK = cls_weight_c scale_c d lml / d K_c -- [B,C,N,N], or [B,N,N] summed over the
+    classes for a shared K --, dscale [B,C] = cls_weight_c <d lml / d K_c, K>)."""
+    per_class = K.dim() == 4
+    K = _req(K, "K", 4 if per_class else 3)
+    Y = _req(Y, "Y", Y.dim() if Y.dim() in (2, 3) else 2)
+    f_hat = _req(f_hat, "f_hat", 3)
+    b_, c_, n = f_hat.shape
+    if (K.shape[0] != b_ or K.shape[-1] != n or K.shape[-2] != n or (per_class and K.shape[1] != c_) or tuple(Y.shape[-2:]) != (c_, n)
+            or (Y.dim() == 3 and Y.shape[0] != b_)):
+        raise RuntimeError("laplace_grad: K %s / Y %s do not fit f_hat %s" % (tuple(K.shape), tuple(Y.shape), tuple(f_hat.shape)))
+    cw = None if cls_weight is None else _req(cls_weight.reshape(-1), "cls_weight", 1)
+    sc = None if scale is None else _req(scale.reshape(-1), "scale", 1)
+    if (cw is not None and cw.numel() != c_) or (sc is not None and sc.numel() != c_):
+        raise RuntimeError("laplace_grad: cls_weight / scale must have C=%d elements" % c_)
+    dev = K.device
+    lml = torch.empty((b_, c_), device=dev, dtype=torch.float32)
+    dscale = torch.empty((b_, c_), device=dev, dtype=torch.float32)
+    dk = torch.empty((b_, c_, n, n) if per_class else (b_, n, n), device=dev, dtype=torch.float32)
+    lib = _lib_now()
+    ws_bytes = 0 if per_class else int(lib.dkt_laplace_grad_workspace_bytes(b_, c_, n))
+    ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32) if ws_bytes else None
+    with _timed("dkt_laplace_grad_f32"):
+        st = lib.dkt_laplace_grad_f32(_p(K), (c_ if per_class else 1) * n * n, n * n if per_class else 0, _p(sc), _p(Y), c_ * n if Y.dim() == 3 else 0,
+                                      _p(f_hat), _p(cw), _p(lml), _p(dk), _p(dscale), b_, c_, n, _p(ws), ws_bytes, _stream())
+    _lib.check(st, "dkt_laplace_grad_f32")
+    return lml, dk, dscale
+
+
+def _laplace_forward(K, Y, cls_weight, scale, max_iter):
+    """mode (no autograd) -> lml and its gradient at the mode -> obj[b] = sum_c cls_weight[c] lml[b,c].  No read-back."""
+    with torch.no_grad():
+        if scale is None:
+            kc = K
+        else:                                 # dkt_gpc_mode_f32 takes the covariances themselves: a transient [B,C,N,N] (dkt_laplace_grad_f32 reads K and scale)
+            kc = (K if K.dim() == 4 else K.unsqueeze(1)) * scale.reshape(1, -1, 1, 1)
+        md = laplace_mode(kc, Y, max_iter)
+        lml, dk, dscale = laplace_grad(K, Y, md["f"], cls_weight, scale)
+        return objective(lml, cls_weight), lml, md["iters"], dk, dscale
+
+
+class _LaplaceObjectiveFn(torch.autograd.Function):
+    """obj[b] = sum_c cls_weight[c] lml[b,c] of the Laplace approximation at the mode; backward grad_out * dK, grad_out * dscale."""
+
+    @staticmethod
+    def forward(ctx, K, Y, cls_weight, scale, max_iter):
+        obj, lml, iters, dk, dscale = _laplace_forward(K, Y, cls_weight, scale, max_iter)
+        ctx.save_for_backward(dk, dscale)
+        ctx.scale_shape = None if scale is None else scale.shape
+        ctx.mark_non_differentiable(lml, iters)
+        ctx.set_materialize_grads(False)
+        return obj, lml, iters
+
+    @staticmethod
+    def backward(ctx, gobj, *_unused):
+        if gobj is None:
+            return (None,) * 5
+        dk, dscale = ctx.saved_tensors
+        gobj = gobj.contiguous()
+        gk = dk * gobj.reshape([-1] + [1] * (dk.dim() - 1)) if ctx.needs_input_grad[0] else None
+        gs = (gobj.reshape(-1, 1) * dscale).sum(0).reshape(ctx.scale_shape) if (ctx.scale_shape is not None and ctx.needs_input_grad[3]) else None
+        return gk, None, None, gs, None
+
+
+def laplace_objective(K, Y, cls_weight, scale=None, max_iter: int = 100):
+    """Differentiable (in K and scale) Laplace training objective of B episodes: returns (obj [B], lml [B,C], iters [B,C]); arguments as `laplace_grad`.
+    Forward: `laplace_mode` without autograd, then `laplace_grad`; no host read-back (graph-capturable like the other episode calls)."""
+    return _LaplaceObjectiveFn.apply(K, Y, cls_weight, scale, max_iter)
+
+
+class _EpisodeLaplaceLinearFn(torch.autograd.Function):
+    """Bernoulli-likelihood training episode for the linear kinds: E = Z Z^T (dkt_gram_f32) -> mode, lml, dE (shared E, scale = outputscale);
+    backward dZ = g_b (dE + dE^T) Z (dkt_gram_bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, z, y, sv, cls_weight, unit_rows, max_iter):
+        e = gram(z, None, KERNEL_LINEAR_UNIT if unit_rows else KERNEL_LINEAR)
+        obj, lml, iters, dk, dscale = _laplace_forward(e, y, cls_weight, sv.detach(), max_iter)
+        ctx.save_for_backward(z, dk, dscale)
+        ctx.unit_rows, ctx.sv_shape = bool(unit_rows), sv.shape
+        ctx.mark_non_differentiable(lml, iters, e)
+        ctx.set_materialize_grads(False)
+        return obj, lml, iters, e
+
+    @staticmethod
+    def backward(ctx, gobj, *_unused):
+        if gobj is None:
+            return (None,) * 6
+        z, dk, dscale = ctx.saved_tensors
+        gobj = gobj.contiguous()
+        dz = gram_bwd(dk, z, gobj, unit_rows=ctx.unit_rows, w_symmetric=True) if ctx.needs_input_grad[0] else None
+        gsv = (gobj.reshape(-1, 1) * dscale).sum(0).reshape(ctx.sv_shape) if ctx.needs_input_grad[2] else None
+        return dz, None, gsv, None, None, None
+
+
+class _EpisodeLaplaceClassKernelFn(torch.autograd.Function):
+    """The same for rbf / matern / poli: one contraction -> the C class kernels -> mode, lml, dE [B,C,N,N]; backward dkt_class_kernel_bwd_f32 -> dkt_gram_bwd_f32."""
+
+    @staticmethod
+    def forward(ctx, z, y, sv, cls_weight, param, cmap, power, base_kind, max_iter):
+        one = torch.ones(1, device=z.device, dtype=torch.float32)
+        base = gram(z, None, base_kind, one if base_kind == KERNEL_SQDIST else None)
+        e = class_kernel(base, cmap, power, param.detach())
+        obj, lml, iters, dk, dscale = _laplace_forward(e, y, cls_weight, sv.detach(), max_iter)
+        ctx.save_for_backward(z, base, dk, dscale, param)
+        ctx.maps, ctx.shapes = (int(cmap), int(power)), (sv.shape, param.shape)
+        ctx.mark_non_differentiable(lml, iters, e)
+        ctx.set_materialize_grads(False)
+        return obj, lml, iters, e
+
+    @staticmethod
+    def backward(ctx, gobj, *_unused):
+        if gobj is None:
+            return (None,) * 9
+        z, base, dk, dscale, param = ctx.saved_tensors
+        gobj = gobj.contiguous()
+        ng = ctx.needs_input_grad
+        dz = gparam = None
+        if ng[0] or ng[4]:
+            wp, dpar = class_kernel_bwd(dk, base, ctx.maps[0], ctx.maps[1], param)
+            if ng[0]:
+                dz = gram_bwd(wp, z, gobj)
+            if ng[4]:
+                gparam = (gobj.reshape(-1, 1) * dpar).sum(0).reshape(ctx.shapes[1])
+        gsv = (gobj.reshape(-1, 1) * dscale).sum(0).reshape(ctx.shapes[0]) if ng[2] else None
+        return dz, None, gsv, None, gparam, None, None, None, None
+
+
+def episode_loss_laplace(z, y, sv, cls_weight, kernel: str, lengthscale=None, offset=None, unit_rows: bool = False, max_iter: int = 100):
+    """Bernoulli-likelihood training episode(s) z [B,N,D] (N <= 127, C <= 32), y in {0,1}: K_c = sv_c * k_c(z, z).  Returns (obj [B], lml [B,C], iters [B,C], E)."""
+    z = _req(z, "z", 3)
+    if kernel in LINEAR_KINDS:
+        return _EpisodeLaplaceLinearFn.apply(z, y, sv, cls_weight, bool(unit_rows), max_iter)
+    cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
+    return _EpisodeLaplaceClassKernelFn.apply(z, y, sv, cls_weight, param, cmap, power, base_kind, max_iter)
 
 
 def _classmap_of(kernel: str, lengthscale, offset):
@@ -1255,6 +1395,55 @@ class _EpisodeLossBnFn(torch.autograd.Function):
             gbeta = sb.reshape(ctx.shapes[4]) if (ng[2] and ctx.shapes[4] is not None) else None
         gsv, gmean, gnoise = hyper_grads(gobj, cw, dsv if ng[6] else None, dmean if ng[7] else None, dnoise if ng[8] else None, ctx.shapes[:3])
         return (dx if ng[0] else None), ggamma, gbeta, None, None, None, gsv, gmean, gnoise, None, None, None
+
+
+class _EpisodeLaplaceBnFn(torch.autograd.Function):
+    """Bernoulli-likelihood training episode straight from the trunk output X (N <= 127): the front end of `_EpisodeLossBnFn` (statistics + Gram in one pass,
+    the normalised features never written) -> mode, lml, dE -> backward dkt_gram_bn_bwd_f32, which takes dE exactly as it takes the Gaussian W."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, use_bn, y, sv, cls_weight, max_iter):
+        d = x.shape[2]
+        if use_bn and os.environ.get("DKT_FUSED_STATS", "1") != "0":
+            e, rnorm, st = gram_bn_train(x, gamma, beta, eps)               # statistics + Gram in one pass over x
+            a, s, bmean, rstd, bvar = st["a"], st["s"], st["mean"], st["rstd"], st["var_unbiased"]
+        else:
+            if use_bn:
+                st = bn_stats(x, gamma, beta, eps)
+                a, s, bmean, rstd, bvar = st["a"], st["s"], st["mean"], st["rstd"], st["var_unbiased"]
+            else:
+                a = torch.ones(d, device=x.device, dtype=torch.float32)
+                s = torch.zeros(d, device=x.device, dtype=torch.float32)
+                bmean = rstd = bvar = torch.zeros(0, device=x.device, dtype=torch.float32)
+            e, rnorm = gram_bn(x, a, s)
+        obj, lml, iters, dk, dscale = _laplace_forward(e, y, cls_weight, sv.detach(), max_iter)
+        ctx.use_bn = bool(use_bn)
+        ctx.save_for_backward(x, e, dk, a, s, bmean, rstd, rnorm, dscale)
+        ctx.shapes = (sv.shape, None if gamma is None else gamma.shape, None if beta is None else beta.shape)
+        ctx.mark_non_differentiable(lml, iters, e, bmean, bvar, a, s, rnorm)
+        ctx.set_materialize_grads(False)
+        return obj, lml, iters, e, bmean, bvar, a, s, rnorm
+
+    @staticmethod
+    def backward(ctx, gobj, *_unused):
+        if gobj is None:
+            return (None,) * 9
+        x, e, dk, a, s, bmean, rstd, rnorm, dscale = ctx.saved_tensors
+        gobj = gobj.contiguous()
+        dx, dg, db = gram_bn_bwd(dk, e, x, a, s, rnorm, bmean if ctx.use_bn else None, rstd if ctx.use_bn else None, gobj)
+        ng = ctx.needs_input_grad
+        ggamma = gbeta = None
+        if dg is not None and ((ng[1] and ctx.shapes[1] is not None) or (ng[2] and ctx.shapes[2] is not None)):
+            sg, sb = bn_param_grads(dg, db)
+            ggamma = sg.reshape(ctx.shapes[1]) if (ng[1] and ctx.shapes[1] is not None) else None
+            gbeta = sb.reshape(ctx.shapes[2]) if (ng[2] and ctx.shapes[2] is not None) else None
+        gsv = (gobj.reshape(-1, 1) * dscale).sum(0).reshape(ctx.shapes[0]) if ng[6] else None
+        return (dx if ng[0] else None), ggamma, gbeta, None, None, None, gsv, None, None
+
+
+def episode_loss_laplace_bn(x, gamma, beta, y, sv, cls_weight, eps: float = 1e-5, use_bn: bool = True, max_iter: int = 100):
+    """x [B,N,D] trunk output BEFORE bn_out, N <= 127.  Returns (obj [B], lml, iters, E, batch_mean, batch_var_unbiased, a, s, rnorm)."""
+    return _EpisodeLaplaceBnFn.apply(x, gamma, beta, eps, use_bn, y, sv, cls_weight, max_iter)
 
 
 def episode_loss_bn(x, gamma, beta, y, sv, mean, noise, cls_weight, eps: float = 1e-5, jitter0: float = 1e-6, max_tries: int = 3,

@@ -43,6 +43,9 @@ extern "C" {
 #define DKT_ERR_TOO_LARGE (-2)
 #define DKT_ERR_WORKSPACE (-3)
 #define DKT_ERR_LAUNCH (-4)
+#ifndef DKT_ERR_SHAPE
+#define DKT_ERR_SHAPE (-5) /* a size outside the limits a call states (dkt_laplace_grad_f32; the calls of dkt_abi_gpc.h) */
+#endif
 
 /* base-kernel kinds (configs.py:7 kernel_type; DKT.py:352-370) */
 #define DKT_KERNEL_LINEAR 0 /* linear / cossim / bncossim : E = A B^T                       */
@@ -388,6 +391,30 @@ int dkt_smk_f32(const float* x1, const float* x2, const float* weights, const fl
 int dkt_smk_bwd_f32(const float* gE, const float* Eq, const float* x, const float* weights, const float* means,
                     const float* scales, float* dx, float* dmeans, float* dscales, int B, int N, int D, int Q,
                     void* stream);
+
+/*
+ * ---- training under a Bernoulli likelihood: the Laplace approximation of the log marginal likelihood and its gradient -----------------
+ * (an additive entry of ABI 7; GPML algorithm 5.1 in matrix form, docs/LAPLACE.md "Training")
+ * Problem (b, c): prior covariance scale[c] * (K + b k_batch_stride + c k_class_stride) ([N,N]; k_class_stride 0: the C problems of an episode
+ * share one K, e.g. the linear kernels' K_c = outputscale_c E with no [B,C,N,N] tensor in memory), targets in {0,1} at Y + b y_batch_stride + c N
+ * (y_batch_stride 0: every episode has the same targets [C,N]), mode f_hat [B,C,N] from dkt_gpc_mode_f32 (include/dkt_abi_gpc.h) on the same
+ * covariances.  Strides count elements; scale [C] or NULL (= 1); cls_weight [C] or NULL (= 1), as in dkt_mll_f32.  Everything is evaluated AT f_hat:
+ *     pi = sigmoid(f), W = pi (1 - pi), g = y - pi, L = chol(I + W^1/2 K W^1/2), R = W^1/2 (I + W^1/2 K W^1/2)^-1 W^1/2
+ *     lml = -1/2 g.f - sum log(1 + exp(-(2y - 1) f)) - sum log L_ii
+ *     s2 = -1/2 (diag K - diag(K R K)) pi (1 - pi) (1 - 2 pi),  u = s2 - R K s2,  G = d lml / d K = 1/2 (g g^T - R) + 1/2 (u g^T + g u^T)
+ * Outputs: lml [B,C] (unweighted);  per-class K: dK [B,C,N,N], dK[b,c] = cls_weight[c] scale[c] G_c;  shared K: dK [B,N,N] =
+ * sum_c cls_weight[c] scale[c] G_c, the classes in index order (needs the workspace: dkt_laplace_grad_workspace_bytes(B, C, N) bytes; the
+ * per-class form needs none);  dscale [B,C] (may be NULL) = cls_weight[c] <G_c, K>.  Plain fp32, no atomics: two runs give the same bits, and a
+ * shared call's dK is bit for bit the in-order sum of the per-class call's.
+ * Limits (DKT_ERR_SHAPE outside them, before any launch): 1 <= N <= DKT_LAPLACE_MAX_N, 1 <= C <= DKT_LAPLACE_MAX_C.
+ * Replaces, for a Bernoulli likelihood, what dkt_mll_f32 replaces for the Gaussian one (methods/DKT.py:161-163).
+ */
+#define DKT_LAPLACE_MAX_N 127
+#define DKT_LAPLACE_MAX_C 32
+size_t dkt_laplace_grad_workspace_bytes(int B, int C, int N);
+int dkt_laplace_grad_f32(const float* K, long k_batch_stride, long k_class_stride, const float* scale, const float* Y, long y_batch_stride,
+                         const float* f_hat, const float* cls_weight, float* lml, float* dK, float* dscale, int B, int C, int N,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
