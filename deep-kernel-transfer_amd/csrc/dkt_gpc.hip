@@ -10,31 +10,19 @@
 // Predict: a wave per 64 query points of an episode, looping over the classes (the label needs all of them): the class's factor L in LDS, a
 // lane solves L v = w_sr * ks for its own query (v in LDS, column per lane), var = kss - |v|^2.  The five-term mixture is summed in double:
 // its coefficients are about +-2000..3500 and sum to 1, in fp32 the cancellation costs 1e-4 of the probability.
-#include <hip/hip_runtime.h>
-#include <math.h>
-
-#include "../../include/dkt_abi.h"
 #include "../../include/dkt_abi_gpc.h"
+#include "dkt_laplace_lds.h"
 
 namespace {
 
-constexpr int kWave = 64;
+using namespace dkt_laplace;             // padded, wave_sum, stage_matrix, build_b_lower, cholesky_lower, lml_term, set_lds
 constexpr int kVecs = 8;                 // LDS vectors of the mode kernel, 128 floats each
 constexpr int kVec = 128;
 constexpr int kQT = 64;                  // query points per workgroup of the predict kernel (a lane each)
 constexpr int kQS = kQT + 1;             // row stride of the per-lane columns (odd: the staging writes do not collide)
 
-__host__ __device__ inline int padded(int N) { return N | 1; }          // odd row stride: a column walk touches every bank
-
 inline size_t mode_lds_bytes(int N) { return ((size_t)2 * N * padded(N) + kVecs * kVec) * sizeof(float); }
 inline size_t predict_lds_bytes(int N) { return ((size_t)N * padded(N) + (size_t)N * kQS + 2 * kVec) * sizeof(float); }
-
-// sum over the wave, the same value in every lane (the pairs commute: x + y in one lane, y + x in its partner)
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
 
 template <int T>
 __global__ __launch_bounds__(T) void gpc_mode_kernel(const float* __restrict__ K, long kbs, long kcs, const float* __restrict__ Y, long ybs,
@@ -58,10 +46,7 @@ __global__ __launch_bounds__(T) void gpc_mode_kernel(const float* __restrict__ K
     const float* Kp = K + (long)b * kbs + (long)c * kcs;
     const float* Yp = Y + (long)b * ybs + (long)c * N;
 
-    for (int idx = tid; idx < N * N; idx += T) {
-        int i = idx / N, j = idx - i * N;
-        sK[i * NP + j] = Kp[idx];
-    }
+    stage_matrix<T>(sK, Kp, N, NP, tid);
     if (tid < N) {
         sy[tid] = Yp[tid];
         sf[tid] = 0.f;
@@ -83,28 +68,14 @@ __global__ __launch_bounds__(T) void gpc_mode_kernel(const float* __restrict__ K
         }
         __syncthreads();
         // B = I + W^1/2 K W^1/2 (lower triangle) and t = W^1/2 K b
-        for (int idx = tid; idx < N * N; idx += T) {
-            int i = idx / N, j = idx - i * N;
-            if (j <= i) sA[i * NP + j] = (i == j ? 1.f : 0.f) + (sw[i] * sK[i * NP + j]) * sw[j];
-        }
+        build_b_lower<T>(sA, sK, sw, N, NP, tid);
         if (tid < N) {
             float acc = 0.f;
             for (int j = 0; j < N; ++j) acc += sK[tid * NP + j] * sb[j];
             st[tid] = sw[tid] * acc;
         }
         __syncthreads();
-        // right-looking Cholesky: column j scaled by its pivot (kept apart in sd: the pivot entry itself is only read here), then the trailing update
-        for (int j = 0; j < N; ++j) {
-            float d = sqrtf(sA[j * NP + j]);
-            for (int i = j + 1 + tid; i < N; i += T) sA[i * NP + j] = sA[i * NP + j] / d;
-            if (tid == 0) sd[j] = d;
-            __syncthreads();
-            for (int i = j + 1 + tid / 16; i < N; i += T / 16) {
-                float lij = sA[i * NP + j];
-                for (int k = j + 1 + (tid & 15); k <= i; k += 16) sA[i * NP + k] -= lij * sA[k * NP + j];
-            }
-            __syncthreads();
-        }
+        cholesky_lower<T>(sA, sd, N, NP, tid);
         // a = b - W^1/2 L^-T L^-1 t, one wave, rows `lane` and `lane + 64` in registers
         if (tid < kWave) {
             const int i0 = lane, i1 = lane + kWave;
@@ -127,13 +98,12 @@ __global__ __launch_bounds__(T) void gpc_mode_kernel(const float* __restrict__ K
             if (i1 < N) sb[i1] = sb[i1] - sw[i1] * u1;
         }
         __syncthreads();
-        // f = K a and the terms of the log marginal likelihood (log(1 + exp(-z)) = max(-z, 0) + log1p(exp(-|z|)): no overflow for large |f|)
+        // f = K a and the terms of the log marginal likelihood
         if (tid < N) {
             float acc = 0.f;
             for (int j = 0; j < N; ++j) acc += sK[tid * NP + j] * sb[j];
             sf[tid] = acc;
-            float z = (2.f * sy[tid] - 1.f) * acc;
-            st[tid] = -0.5f * sb[tid] * acc - (fmaxf(-z, 0.f) + log1pf(expf(-fabsf(z)))) - logf(sd[tid]);
+            st[tid] = lml_term(sy[tid], sb[tid], acc, sd[tid]);
         }
         __syncthreads();
         float lml = wave_sum((lane < N ? st[lane] : 0.f) + (lane + kWave < N ? st[lane + kWave] : 0.f));       // every wave gets the same bits
@@ -200,10 +170,7 @@ __global__ __launch_bounds__(kQT) void gpc_predict_kernel(const float* __restric
         const float* Lp = Lc + pc * (long)N * N;
         const float* Kp = Ks + (long)b * ksbs + (long)c * kscs + q0 * N;
         __syncthreads();
-        for (int idx = lane; idx < N * N; idx += kQT) {
-            int i = idx / N, j = idx - i * N;
-            sL[i * NP + j] = Lp[idx];
-        }
+        stage_matrix<kQT>(sL, Lp, N, NP, lane);
         for (int idx = lane; idx < kQT * N; idx += kQT) {          // rows q0 .. q0 + nq - 1 of Ks, read along the rows; zeros for the lanes past M
             int qq = idx / N, n = idx - qq * N;
             sv[n * kQS + qq] = qq < nq ? Kp[idx] : 0.f;
@@ -238,11 +205,6 @@ __global__ __launch_bounds__(kQT) void gpc_predict_kernel(const float* __restric
         }
     }
     if (labels && lane < nq) labels[(long)b * M + q] = C == 1 ? (mu1 > 0.f ? 1 : 0) : label;
-}
-
-int set_lds(const void* fn, size_t bytes) {
-    if (bytes <= 64 * 1024) return DKT_OK;
-    return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;
 }
 
 }  // namespace

@@ -8,27 +8,16 @@
 // time, G is written straight from R, g, u.  A shared K (class stride 0) has its classes summed by pass 1 of the SAME kernel (an element per thread,
 // the classes in index order) from the per-class matrices pass 0 left in the workspace: no atomics, and the sum of a shared call is bit for bit the
 // sum of the per-class call's outputs.  Plain fp32 on the VALU; every reduction has a fixed order that depends on nothing but N.
-#include <hip/hip_runtime.h>
-#include <math.h>
-
-#include "../../include/dkt_abi.h"
+#include "dkt_laplace_lds.h"
 
 namespace {
 
+using namespace dkt_laplace;             // padded, wave_sum, stage_matrix, build_b_lower, cholesky_lower, lml_term, set_lds
 constexpr int kT = 256;
-constexpr int kWave = 64;
 constexpr int kVec = 128;
 constexpr int kVecs = 10;                // sf .. sred below
 
-__host__ __device__ inline int padded(int N) { return N | 1; }          // odd row stride: a column walk touches every bank
 inline size_t grad_lds_bytes(int N) { return ((size_t)2 * N * padded(N) + kVecs * kVec) * sizeof(float); }
-
-// sum over the wave, the same value in every lane
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
 
 __global__ __launch_bounds__(kT) void laplace_grad_kernel(const float* __restrict__ K, long kbs, long kcs, const float* __restrict__ scale,
                                                          const float* __restrict__ Y, long ybs, const float* __restrict__ F,
@@ -70,10 +59,7 @@ __global__ __launch_bounds__(kT) void laplace_grad_kernel(const float* __restric
     const float sc = scale ? scale[c] : 1.f;
     const float wc = cw ? cw[c] : 1.f;
 
-    for (int idx = tid; idx < NN; idx += kT) {
-        int i = idx / N, j = idx - i * N;
-        sK[i * NP + j] = sc * Kp[idx];
-    }
+    stage_matrix<kT, true>(sK, Kp, N, NP, tid, sc);
     if (tid < N) {
         const float f = F[prob * N + tid], y = Yp[tid];
         const float pi = 1.f / (1.f + expf(-f));
@@ -84,29 +70,13 @@ __global__ __launch_bounds__(kT) void laplace_grad_kernel(const float* __restric
         s3[tid] = w * (1.f - 2.f * pi);
     }
     __syncthreads();
-    // B = I + W^1/2 K W^1/2, lower triangle
-    for (int idx = tid; idx < NN; idx += kT) {
-        int i = idx / N, j = idx - i * N;
-        if (j <= i) sA[i * NP + j] = (i == j ? 1.f : 0.f) + (sw[i] * sK[i * NP + j]) * sw[j];
-    }
+    build_b_lower<kT>(sA, sK, sw, N, NP, tid);
     __syncthreads();
-    // right-looking Cholesky (as dkt_gpc.hip): column j scaled by its pivot (kept in sd), then the trailing update
-    for (int j = 0; j < N; ++j) {
-        float d = sqrtf(sA[j * NP + j]);
-        for (int i = j + 1 + tid; i < N; i += kT) sA[i * NP + j] = sA[i * NP + j] / d;
-        if (tid == 0) sd[j] = d;
-        __syncthreads();
-        for (int i = j + 1 + tid / 16; i < N; i += kT / 16) {
-            float lij = sA[i * NP + j];
-            for (int k = j + 1 + (tid & 15); k <= i; k += 16) sA[i * NP + k] -= lij * sA[k * NP + j];
-        }
-        __syncthreads();
-    }
-    // lml = -1/2 g.f - sum log(1 + exp(-(2y - 1) f)) - sum log L_ii    (log(1 + exp(-z)) = max(-z, 0) + log1p(exp(-|z|)))
+    cholesky_lower<kT>(sA, sd, N, NP, tid);
+    // lml = -1/2 g.f - sum log(1 + exp(-(2y - 1) f)) - sum log L_ii
     if (tid < N) {
         const float f = sf[tid], g = sg[tid];
-        const float z = (2.f * Yp[tid] - 1.f) * f;
-        st[tid] = -0.5f * g * f - (fmaxf(-z, 0.f) + log1pf(expf(-fabsf(z)))) - logf(sd[tid]);
+        st[tid] = lml_term(Yp[tid], g, f, sd[tid]);
         sA[tid * NP + tid] = 1.f / sd[tid];                       // U_ii
     }
     __syncthreads();
@@ -209,9 +179,7 @@ extern "C" int dkt_laplace_grad_f32(const float* K, long k_batch_stride, long k_
     if (shared && (!workspace || workspace_bytes < dkt_laplace_grad_workspace_bytes(B, C, N))) return DKT_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = grad_lds_bytes(N);
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)laplace_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DKT_ERR_LAUNCH;
+    if (set_lds((const void*)laplace_grad_kernel, lds) != DKT_OK) return DKT_ERR_LAUNCH;
     float* g_out = shared ? (float*)workspace : dK;
     hipLaunchKernelGGL(laplace_grad_kernel, dim3((unsigned)(B * C)), dim3(kT), lds, st, K, k_batch_stride, k_class_stride, scale, Y,
                        y_batch_stride, f_hat, cls_weight, lml, g_out, dK, dscale, B, C, N, 0);

@@ -709,102 +709,6 @@ def _laplace_forward(K, Y, cls_weight, scale, max_iter):
         return objective(lml, cls_weight), lml, md["iters"], dk, dscale
 
 
-class _LaplaceObjectiveFn(torch.autograd.Function):
-    """obj[b] = sum_c cls_weight[c] lml[b,c] of the Laplace approximation at the mode; backward grad_out * dK, grad_out * dscale."""
-
-    @staticmethod
-    def forward(ctx, K, Y, cls_weight, scale, max_iter):
-        obj, lml, iters, dk, dscale = _laplace_forward(K, Y, cls_weight, scale, max_iter)
-        ctx.save_for_backward(dk, dscale)
-        ctx.scale_shape = None if scale is None else scale.shape
-        ctx.mark_non_differentiable(lml, iters)
-        ctx.set_materialize_grads(False)
-        return obj, lml, iters
-
-    @staticmethod
-    def backward(ctx, gobj, *_unused):
-        if gobj is None:
-            return (None,) * 5
-        dk, dscale = ctx.saved_tensors
-        gobj = gobj.contiguous()
-        gk = dk * gobj.reshape([-1] + [1] * (dk.dim() - 1)) if ctx.needs_input_grad[0] else None
-        gs = (gobj.reshape(-1, 1) * dscale).sum(0).reshape(ctx.scale_shape) if (ctx.scale_shape is not None and ctx.needs_input_grad[3]) else None
-        return gk, None, None, gs, None
-
-
-def laplace_objective(K, Y, cls_weight, scale=None, max_iter: int = 100):
-    """Differentiable (in K and scale) Laplace training objective of B episodes: returns (obj [B], lml [B,C], iters [B,C]); arguments as `laplace_grad`.
-    Forward: `laplace_mode` without autograd, then `laplace_grad`; no host read-back (graph-capturable like the other episode calls)."""
-    return _LaplaceObjectiveFn.apply(K, Y, cls_weight, scale, max_iter)
-
-
-class _EpisodeLaplaceLinearFn(torch.autograd.Function):
-    """Bernoulli-likelihood training episode for the linear kinds: E = Z Z^T (dkt_gram_f32) -> mode, lml, dE (shared E, scale = outputscale);
-    backward dZ = g_b (dE + dE^T) Z (dkt_gram_bwd_f32)."""
-
-    @staticmethod
-    def forward(ctx, z, y, sv, cls_weight, unit_rows, max_iter):
-        e = gram(z, None, KERNEL_LINEAR_UNIT if unit_rows else KERNEL_LINEAR)
-        obj, lml, iters, dk, dscale = _laplace_forward(e, y, cls_weight, sv.detach(), max_iter)
-        ctx.save_for_backward(z, dk, dscale)
-        ctx.unit_rows, ctx.sv_shape = bool(unit_rows), sv.shape
-        ctx.mark_non_differentiable(lml, iters, e)
-        ctx.set_materialize_grads(False)
-        return obj, lml, iters, e
-
-    @staticmethod
-    def backward(ctx, gobj, *_unused):
-        if gobj is None:
-            return (None,) * 6
-        z, dk, dscale = ctx.saved_tensors
-        gobj = gobj.contiguous()
-        dz = gram_bwd(dk, z, gobj, unit_rows=ctx.unit_rows, w_symmetric=True) if ctx.needs_input_grad[0] else None
-        gsv = (gobj.reshape(-1, 1) * dscale).sum(0).reshape(ctx.sv_shape) if ctx.needs_input_grad[2] else None
-        return dz, None, gsv, None, None, None
-
-
-class _EpisodeLaplaceClassKernelFn(torch.autograd.Function):
-    """The same for rbf / matern / poli: one contraction -> the C class kernels -> mode, lml, dE [B,C,N,N]; backward dkt_class_kernel_bwd_f32 -> dkt_gram_bwd_f32."""
-
-    @staticmethod
-    def forward(ctx, z, y, sv, cls_weight, param, cmap, power, base_kind, max_iter):
-        one = torch.ones(1, device=z.device, dtype=torch.float32)
-        base = gram(z, None, base_kind, one if base_kind == KERNEL_SQDIST else None)
-        e = class_kernel(base, cmap, power, param.detach())
-        obj, lml, iters, dk, dscale = _laplace_forward(e, y, cls_weight, sv.detach(), max_iter)
-        ctx.save_for_backward(z, base, dk, dscale, param)
-        ctx.maps, ctx.shapes = (int(cmap), int(power)), (sv.shape, param.shape)
-        ctx.mark_non_differentiable(lml, iters, e)
-        ctx.set_materialize_grads(False)
-        return obj, lml, iters, e
-
-    @staticmethod
-    def backward(ctx, gobj, *_unused):
-        if gobj is None:
-            return (None,) * 9
-        z, base, dk, dscale, param = ctx.saved_tensors
-        gobj = gobj.contiguous()
-        ng = ctx.needs_input_grad
-        dz = gparam = None
-        if ng[0] or ng[4]:
-            wp, dpar = class_kernel_bwd(dk, base, ctx.maps[0], ctx.maps[1], param)
-            if ng[0]:
-                dz = gram_bwd(wp, z, gobj)
-            if ng[4]:
-                gparam = (gobj.reshape(-1, 1) * dpar).sum(0).reshape(ctx.shapes[1])
-        gsv = (gobj.reshape(-1, 1) * dscale).sum(0).reshape(ctx.shapes[0]) if ng[2] else None
-        return dz, None, gsv, None, gparam, None, None, None, None
-
-
-def episode_loss_laplace(z, y, sv, cls_weight, kernel: str, lengthscale=None, offset=None, unit_rows: bool = False, max_iter: int = 100):
-    """Bernoulli-likelihood training episode(s) z [B,N,D] (N <= 127, C <= 32), y in {0,1}: K_c = sv_c * k_c(z, z).  Returns (obj [B], lml [B,C], iters [B,C], E)."""
-    z = _req(z, "z", 3)
-    if kernel in LINEAR_KINDS:
-        return _EpisodeLaplaceLinearFn.apply(z, y, sv, cls_weight, bool(unit_rows), max_iter)
-    cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
-    return _EpisodeLaplaceClassKernelFn.apply(z, y, sv, cls_weight, param, cmap, power, base_kind, max_iter)
-
-
 def _classmap_of(kernel: str, lengthscale, offset):
     """(map id, power, parameter [C], base-matrix kind) of a kernel whose class models own their base-kernel parameter."""
     if kernel in POLY_KINDS:
@@ -849,59 +753,11 @@ def class_kernel_bwd(w: torch.Tensor, base: torch.Tensor, cmap: int, power: int,
     return wp, (dparam[:, 0] if nsplit == 1 else dparam.sum(1))
 
 
-class _EpisodeLossClassKernelFn(torch.autograd.Function):
-    """Fused training episode for the kernels whose class models own a base-kernel parameter (rbf / matern: lengthscale [C]; poli1 / poli2:
-    offset [C]; reference DKT.py:63-66, 352-365):
-       forward : ONE contraction per episode (dkt_gram_f32: squared distances or Gram) -> the C class kernels (dkt_class_kernel_f32)
-                 -> logp, W[B,C,N,N], hyper grads in ONE launch (dkt_mll_f32, DKT_MLL_E_PER_CLASS)
-       backward: dkt_class_kernel_bwd_f32 (sum over the classes, parameter gradients) -> dkt_gram_bwd_f32 (upstream grad as ep_scale)."""
-
-    @staticmethod
-    def forward(ctx, z, y, sv, mean, noise, cls_weight, param, cmap, power, base_kind, jitter0, max_tries):
-        one = torch.ones(1, device=z.device, dtype=torch.float32)
-        base = gram(z, None, base_kind, one if base_kind == KERNEL_SQDIST else None)
-        e = class_kernel(base, cmap, power, param)
-        out = mll(e, y, sv, mean, noise, want_grad=True, cls_weight=cls_weight, jitter0=jitter0, max_tries=max_tries)
-        obj = objective(out["logp"], cls_weight)
-        ctx.save_for_backward(z, base, out["w"], param, out["dsv"], out["dmean"], out["dnoise"], cls_weight)
-        ctx.maps = (int(cmap), int(power))
-        ctx.shapes = (sv.shape, mean.shape, noise.shape, param.shape)
-        ctx.mark_non_differentiable(out["logp"], out["alpha"], out["info"], out["jitter"], e)
-        ctx.set_materialize_grads(False)
-        return obj, out["logp"], out["alpha"], out["info"], out["jitter"], e
-
-    @staticmethod
-    def backward(ctx, gobj, *_unused):
-        if gobj is None:
-            return (None,) * 12
-        z, base, w, param, dsv, dmean, dnoise, cw = ctx.saved_tensors
-        gobj = gobj.contiguous()
-        ng = ctx.needs_input_grad
-        dz = gparam = None
-        if ng[0] or ng[6]:
-            wp, dpar = class_kernel_bwd(w, base, ctx.maps[0], ctx.maps[1], param)
-            if ng[0]:
-                dz = gram_bwd(wp, z, gobj)
-            if ng[6]:
-                gparam = (gobj.reshape(-1, 1) * dpar).sum(0).reshape(ctx.shapes[3])
-        gsv, gmean, gnoise = hyper_grads(gobj, cw, dsv if ng[2] else None, dmean if ng[3] else None, dnoise if ng[4] else None, ctx.shapes[:3])
-        return dz, None, gsv, gmean, gnoise, None, gparam, None, None, None, None, None
-
-
 def mll_per_class_supported(n: int, c: int) -> bool:
     """Sizes the one-launch per-class path serves: dkt_mll_f32 with DKT_MLL_E_PER_CLASS takes every N in one call (N <= 127 one wave per matrix,
     128 <= N <= 447 the tile-array pipeline; both with the jitter ladder); beyond N = 447 its one-launch kernel is the generic one, and the host
     prefers one single-model call per class there (the blocked path serves those).  dkt_class_kernel_bwd_f32: C <= 32."""
     return c <= 32 and n + 1 <= 448
-
-
-def episode_loss_class_kernel(z, y, sv, mean, noise, cls_weight, kernel: str, lengthscale=None, offset=None,
-                              jitter0: float = 1e-6, max_tries: int = 3):
-    """Training episode(s) z:[B,N,D] for rbf / matern / poli1 / poli2 with per-class lengthscale / offset [C], sizes of
-    mll_per_class_supported().
-    Returns (obj[B], logp[B,C], alpha[B,C,N], info[B,C], jitter[B,C], E[B,C,N,N])."""
-    cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
-    return _EpisodeLossClassKernelFn.apply(_req(z, "z", 3), y, sv, mean, noise, cls_weight, param, cmap, power, base_kind, jitter0, max_tries)
 
 
 def base_matrix_per_class(z: torch.Tensor, kernel: str, lengthscale: Optional[torch.Tensor] = None,
@@ -947,30 +803,6 @@ def base_matrix(z: torch.Tensor, kernel: str = "bncossim", lengthscale: Optional
     return _BaseMatrixFn.apply(z, lengthscale, kind)
 
 
-class _MllObjectiveFn(torch.autograd.Function):
-    """obj[b] = sum_c cls_weight[c] logp[b,c]; gradients were produced by the same kernel launch."""
-
-    @staticmethod
-    def forward(ctx, e, y, sv, mean, noise, cls_weight, jitter0, max_tries):
-        out = mll(e, y, sv, mean, noise, want_grad=True, cls_weight=cls_weight, jitter0=jitter0, max_tries=max_tries)
-        obj = objective(out["logp"], cls_weight)
-        ctx.save_for_backward(out["w"], out["dsv"], out["dmean"], out["dnoise"], cls_weight)
-        ctx.shapes = (sv.shape, mean.shape, noise.shape)
-        ctx.mark_non_differentiable(out["logp"], out["alpha"], out["info"], out["jitter"])
-        ctx.set_materialize_grads(False)       # (otherwise autograd zero-fills a gradient tensor for every non-differentiable output)
-        return obj, out["logp"], out["alpha"], out["info"], out["jitter"]
-
-    @staticmethod
-    def backward(ctx, gobj, *_unused):
-        if gobj is None:
-            return (None,) * 8
-        w, dsv, dmean, dnoise, cw = ctx.saved_tensors
-        gobj = gobj.contiguous()
-        ge = w * gobj.reshape([-1] + [1] * (w.dim() - 1)) if ctx.needs_input_grad[0] else None      # w: [B,N,N] or [B,C,N,N] (per-class E)
-        gsv, gmean, gnoise = hyper_grads(gobj, cw, dsv if ctx.needs_input_grad[2] else None, dmean if ctx.needs_input_grad[3] else None, dnoise if ctx.needs_input_grad[4] else None, ctx.shapes[:3])
-        return ge, None, gsv, gmean, gnoise, None, None, None
-
-
 def objective(logp: torch.Tensor, cls_weight: Optional[torch.Tensor]) -> torch.Tensor:
     """obj[b] = sum_c cls_weight[c] logp[b,c] (dkt_objective_f32: one launch, fixed order) -- the sum over the class models of SumMarginalLogLikelihood (DKT.py:70-71, 161)."""
     if os.environ.get("DKT_FUSED_REDUCTIONS", "1") == "0":                 # the tensor expressions (their twin; three launches)
@@ -1000,39 +832,6 @@ def hyper_grads(gobj: torch.Tensor, cls_weight: Optional[torch.Tensor], dsv, dme
     with _timed("dkt_hyper_grads_f32"):
         _lib.check(_lib_now().dkt_hyper_grads_f32(_p(gobj), _p(cw), _p(ds[0]), _p(ds[1]), _p(ds[2]), _p(gs[0]), _p(gs[1]), _p(gs[2]), b_, c_, _stream()), "dkt_hyper_grads_f32")
     return tuple(None if g is None else g.reshape(sh) for g, sh in zip(gs, shapes))
-
-
-def mll_objective(e, y, sv, mean, noise, cls_weight, jitter0: float = 1e-6, max_tries: int = 3):
-    """Returns (obj[B], logp[B,C], alpha[B,C,N], info[B,C], jitter[B,C])."""
-    return _MllObjectiveFn.apply(e, y, sv, mean, noise, cls_weight, jitter0, max_tries)
-
-
-class _EpisodeLossLinearFn(torch.autograd.Function):
-    """Fused training episode for the linear / cossim / bncossim kernel:
-       forward : E = Z Z^T (dkt_gram_f32) -> logp, W, hyper grads (dkt_mll_f32, one launch)
-       backward: dZ = g_b (W + W^T) Z (dkt_gram_bwd_f32, upstream grad folded in as ep_scale)."""
-
-    @staticmethod
-    def forward(ctx, z, y, sv, mean, noise, cls_weight, jitter0, max_tries, unit_rows=False):
-        e = gram(z, None, KERNEL_LINEAR_UNIT if unit_rows else KERNEL_LINEAR)
-        out = mll(e, y, sv, mean, noise, want_grad=True, cls_weight=cls_weight, jitter0=jitter0, max_tries=max_tries)
-        obj = objective(out["logp"], cls_weight)
-        ctx.save_for_backward(z, out["w"], out["dsv"], out["dmean"], out["dnoise"], cls_weight)
-        ctx.shapes = (sv.shape, mean.shape, noise.shape)
-        ctx.unit_rows = bool(unit_rows)
-        ctx.mark_non_differentiable(out["logp"], out["alpha"], out["info"], out["jitter"], e)
-        ctx.set_materialize_grads(False)       # (otherwise autograd zero-fills a gradient tensor for every non-differentiable output: E alone is 361 MB at cfg2)
-        return obj, out["logp"], out["alpha"], out["info"], out["jitter"], e
-
-    @staticmethod
-    def backward(ctx, gobj, *_unused):
-        if gobj is None:
-            return (None,) * 9
-        z, w, dsv, dmean, dnoise, cw = ctx.saved_tensors
-        gobj = gobj.contiguous()
-        dz = gram_bwd(w, z, gobj, unit_rows=ctx.unit_rows, w_symmetric=True) if ctx.needs_input_grad[0] else None   # W: from dkt_mll_f32
-        gsv, gmean, gnoise = hyper_grads(gobj, cw, dsv if ctx.needs_input_grad[2] else None, dmean if ctx.needs_input_grad[3] else None, dnoise if ctx.needs_input_grad[4] else None, ctx.shapes[:3])
-        return dz, None, gsv, gmean, gnoise, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1132,35 +931,6 @@ def _lowrank_backward(z, v, t, wd, gobj) -> torch.Tensor:
         st = lib.dkt_lowrank_bwd_f32(_p(z), _p(v), _p(t), _p(wd), _p(_req(gobj.reshape(-1), "gobj", 1)), _p(dz), b_, v.shape[1], n, d, _stream())
     _lib.check(st, "dkt_lowrank_bwd_f32")
     return dz
-
-
-class _EpisodeLossLowRankFn(torch.autograd.Function):
-    """Training episode of the linear / cossim / bncossim kernel in feature space (D <= 64 < N):
-       forward : A = Z^T Z, P = Z^T (Y - m) (dkt_lowrank_gram_f32) -> the D x D model K'_c = sv_c A + noise_c I through dkt_mll_f32 (jitter ladder and all)
-                 -> alpha, logp, hyper-parameter gradients, V (dkt_lowrank_finish_f32)
-       backward: dZ = g_b (V^T T + 2 Z W') (dkt_lowrank_bwd_f32).
-    Neither E[B,N,N] nor W[B,N,N] is ever formed (reference lines replaced: methods/DKT.py:375-378, 161-163)."""
-
-    @staticmethod
-    def forward(ctx, z, y, sv, mean, noise, cls_weight, jitter0, max_tries, unit_rows):
-        z = _req(z, "z", 3)
-        o = _lowrank_forward(z, _req(y, "y"), _req(sv.reshape(-1), "sv", 1), _req(mean.reshape(-1), "mean", 1), _req(noise.reshape(-1), "noise", 1),
-                             _req(cls_weight.reshape(-1), "cls_weight", 1), jitter0, max_tries, unit_rows)
-        ctx.save_for_backward(z, o["v"], o["t"], o["wd"], o["dsv"], o["dmean"], o["dnoise"], _req(cls_weight.reshape(-1), "cls_weight", 1))
-        ctx.shapes = (sv.shape, mean.shape, noise.shape)
-        ctx.mark_non_differentiable(o["logp"], o["alpha"], o["info"], o["jitter"])
-        ctx.set_materialize_grads(False)
-        return o["obj"], o["logp"], o["alpha"], o["info"], o["jitter"]
-
-    @staticmethod
-    def backward(ctx, gobj, *_unused):
-        if gobj is None:
-            return (None,) * 9
-        z, v, t, wd, dsv, dmean, dnoise, cw = ctx.saved_tensors
-        gobj = gobj.contiguous()
-        dz = _lowrank_backward(z, v, t, wd, gobj) if ctx.needs_input_grad[0] else None
-        gsv, gmean, gnoise = hyper_grads(gobj, cw, dsv if ctx.needs_input_grad[2] else None, dmean if ctx.needs_input_grad[3] else None, dnoise if ctx.needs_input_grad[4] else None, ctx.shapes[:3])
-        return dz, None, gsv, gmean, gnoise, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1308,142 +1078,279 @@ def normalize_bn_bwd(dzn, zn, x, a, rnorm, mean=None, rstd=None):
     return dx, dg, db
 
 
+# ------------------------------------------------------------------------------------------------------
+# Training episodes: a front end (how E is made) x an objective (what is solved on it), behind ONE autograd Function.
+# Both are pairs of plain functions (no autograd) under a class used as a namespace; everything is positional, so a call costs no more host time than a
+# hand-written Function, and a helper names what it reads by unpacking against its own `forward`:
+#   front.forward(objv, *front arguments)  -> (m, outs, saved, static)
+#       m: E -- or, for an objective with `on_features`, the pair (rows Z [B,N,D], unit_rows); outs: its non-differentiable outputs (E first, None where no E
+#       exists); saved: the tensors its backward needs; static: shapes and flags for it
+#   objv.forward(m, *objective arguments)  -> (obj [B], aux, saved, static)
+#       aux: its non-differentiable outputs in the order the public functions return them; saved / static as above
+#   objv.de(saved) -> d obj / d E as the forward left it (W of dkt_mll_f32, dK of dkt_laplace_grad_f32); an `on_features` objective has
+#       objv.drows(z, saved, gobj) -> dZ instead
+#   front.backward(saved, static, objv, osaved, gobj, *needs_input_grad of the front arguments) -> their gradients, a tuple
+#   objv.backward(saved, static, gobj, *needs_input_grad of the objective arguments)            -> their gradients, a tuple
+# `front.nargs` is the number of front arguments.  No route reads anything back to the host: every one is graph-capturable.
+# ------------------------------------------------------------------------------------------------------
+def _sum_episodes(gobj: torch.Tensor, part: torch.Tensor, shape) -> torch.Tensor:
+    """sum_b gobj[b] part[b, :] -- the gradient of a [C] parameter from its per-episode parts [B,C]."""
+    return (gobj.reshape(-1, 1) * part).sum(0).reshape(shape)
 
 
-class _EpisodeLossBnFn(torch.autograd.Function):
-    """Training episode straight from the trunk output X: [BatchNorm1d(train) +] F.normalize + linear Gram
-    (dkt_gram_bn_train_f32; DKT_FUSED_STATS=0: dkt_bn_stats_f32 + dkt_gram_bn_f32) -> MLL (dkt_mll_f32) ; backward dkt_gram_bn_bwd_f32.  The normalised features are
-    never written to memory.  use_bn=False is the plain cossim kernel (no bn_out: affine map = identity).
-    More than 128 rows (the 20-way shapes): dkt_bn_stats_f32 -> dkt_affine_normalize_f32 (Zn written once: the large-N Gram kernels take unit rows as input) ->
-    dkt_gram_f32 -> dkt_mll_f32; backward dkt_gram_bwd_f32 -> dkt_normalize_bn_bwd_f32.
-    X in bfloat16 / float16 (a mixed-precision backbone): the same route through the *_x16 twins of the front-end calls; the gradient of X comes back
-    in X's dtype, everything behind the front end (Zn, E, the marginal likelihood, the hyper-parameter and BatchNorm gradients) is fp32."""
+class _Gaussian:
+    """Exact-GP marginal likelihood on E [B,N,N] or [B,C,N,N]: logp, W = d obj / d E and the hyper-parameter parts in ONE launch (dkt_mll_f32) ->
+    obj[b] = sum_c cls_weight[c] logp[b,c].  Outputs (logp, alpha, info, jitter)."""
+    on_features = resident_only = False
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps, use_bn, y, sv, mean, noise, cls_weight, jitter0, max_tries):
-        b_, n, d = x.shape
-        ctx.lowrank = lowrank_applies(n, d, y.shape[-2], b_, front_end=True)
-        ctx.big = n > FUSED_EP_MAX_N or ctx.lowrank
-        if ctx.big:
-            if use_bn:
-                st = bn_stats(x, gamma, beta, eps)
-                a, s, bmean, rstd, bvar = st["a"], st["s"], st["mean"], st["rstd"], st["var_unbiased"]
-            else:
-                a = torch.ones(d, device=x.device, dtype=torch.float32)
-                s = torch.zeros(d, device=x.device, dtype=torch.float32)
-                bmean = rstd = bvar = torch.zeros(0, device=x.device, dtype=torch.float32)
-            zn, rnorm = affine_normalize(x, a, s)
-            if ctx.lowrank:
-                # D <= 64 < N (Conv4S / Omniglot): the episode in feature space on the normalised features -- no E, no W (csrc/dkt_lowrank.hip)
-                cw_ = _req(cls_weight.reshape(-1), "cls_weight", 1)
-                o = _lowrank_forward(zn, _req(y, "y"), _req(sv.reshape(-1), "sv", 1), _req(mean.reshape(-1), "mean", 1), _req(noise.reshape(-1), "noise", 1),
-                                     cw_, jitter0, max_tries, True)
-                ctx.use_bn = bool(use_bn)
-                ctx.save_for_backward(x, zn, o["wd"], a, s, bmean, rstd, rnorm, o["dsv"], o["dmean"], o["dnoise"], cw_, o["v"], o["t"])
-                ctx.shapes = (sv.shape, mean.shape, noise.shape, None if gamma is None else gamma.shape, None if beta is None else beta.shape)
-                ctx.mark_non_differentiable(o["logp"], o["alpha"], o["info"], o["jitter"], bmean, bvar, a, s, rnorm)
-                ctx.set_materialize_grads(False)
-                return o["obj"], o["logp"], o["alpha"], o["info"], o["jitter"], None, bmean, bvar, a, s, rnorm
-            e = gram(zn, None, KERNEL_LINEAR_UNIT)
-            out = mll(e, y, sv, mean, noise, want_grad=True, cls_weight=cls_weight, jitter0=jitter0, max_tries=max_tries)
-            obj = objective(out["logp"], cls_weight)
-            ctx.use_bn = bool(use_bn)
-            ctx.save_for_backward(x, zn, out["w"], a, s, bmean, rstd, rnorm, out["dsv"], out["dmean"], out["dnoise"], cls_weight)
-            ctx.shapes = (sv.shape, mean.shape, noise.shape, None if gamma is None else gamma.shape, None if beta is None else beta.shape)
-            ctx.mark_non_differentiable(out["logp"], out["alpha"], out["info"], out["jitter"], e, bmean, bvar, a, s, rnorm)
-            ctx.set_materialize_grads(False)
-            return obj, out["logp"], out["alpha"], out["info"], out["jitter"], e, bmean, bvar, a, s, rnorm
-        if use_bn and os.environ.get("DKT_FUSED_STATS", "1") != "0":
-            e, rnorm, st = gram_bn_train(x, gamma, beta, eps)               # statistics + Gram in one pass over x
-            a, s, bmean, rstd, bvar = st["a"], st["s"], st["mean"], st["rstd"], st["var_unbiased"]
-        else:
-            if use_bn:
-                st = bn_stats(x, gamma, beta, eps)
-                a, s, bmean, rstd, bvar = st["a"], st["s"], st["mean"], st["rstd"], st["var_unbiased"]
-            else:
-                a = torch.ones(d, device=x.device, dtype=torch.float32)
-                s = torch.zeros(d, device=x.device, dtype=torch.float32)
-                bmean = rstd = bvar = torch.zeros(0, device=x.device, dtype=torch.float32)
-            e, rnorm = gram_bn(x, a, s)
+    def forward(e, y, sv, mean, noise, cls_weight, jitter0, max_tries):
         out = mll(e, y, sv, mean, noise, want_grad=True, cls_weight=cls_weight, jitter0=jitter0, max_tries=max_tries)
         obj = objective(out["logp"], cls_weight)
-        ctx.use_bn = bool(use_bn)
-        ctx.save_for_backward(x, e, out["w"], a, s, bmean, rstd, rnorm, out["dsv"], out["dmean"], out["dnoise"], cls_weight)
-        ctx.shapes = (sv.shape, mean.shape, noise.shape, None if gamma is None else gamma.shape, None if beta is None else beta.shape)
-        ctx.mark_non_differentiable(out["logp"], out["alpha"], out["info"], out["jitter"], e, bmean, bvar, a, s, rnorm)
-        ctx.set_materialize_grads(False)
-        return obj, out["logp"], out["alpha"], out["info"], out["jitter"], e, bmean, bvar, a, s, rnorm
+        return (obj, (out["logp"], out["alpha"], out["info"], out["jitter"]), (out["w"], out["dsv"], out["dmean"], out["dnoise"], cls_weight),
+                (sv.shape, mean.shape, noise.shape))
 
     @staticmethod
-    def backward(ctx, gobj, *_unused):
-        if gobj is None:
-            return (None,) * 12
-        x, e, w, a, s, bmean, rstd, rnorm, dsv, dmean, dnoise, cw = ctx.saved_tensors[:12]
-        gobj = gobj.contiguous()
-        if ctx.big:                                           # (the second saved tensor is Zn here; feature-space path: the third is W', then V and T)
-            dzn = _lowrank_backward(e, ctx.saved_tensors[12], ctx.saved_tensors[13], w, gobj) if ctx.lowrank else gram_bwd(w, e, gobj, unit_rows=True, w_symmetric=True)
-            dx, dg, db = normalize_bn_bwd(dzn, e, x, a, rnorm, bmean if ctx.use_bn else None, rstd if ctx.use_bn else None)
-        elif ctx.use_bn:
-            dx, dg, db = gram_bn_bwd(w, e, x, a, s, rnorm, bmean, rstd, gobj)
-        else:
-            dx, dg, db = gram_bn_bwd(w, e, x, a, s, rnorm, None, None, gobj)
-        ng = ctx.needs_input_grad
-        ggamma = gbeta = None
-        if dg is not None and ((ng[1] and ctx.shapes[3] is not None) or (ng[2] and ctx.shapes[4] is not None)):
-            sg, sb = bn_param_grads(dg, db)
-            ggamma = sg.reshape(ctx.shapes[3]) if (ng[1] and ctx.shapes[3] is not None) else None
-            gbeta = sb.reshape(ctx.shapes[4]) if (ng[2] and ctx.shapes[4] is not None) else None
-        gsv, gmean, gnoise = hyper_grads(gobj, cw, dsv if ng[6] else None, dmean if ng[7] else None, dnoise if ng[8] else None, ctx.shapes[:3])
-        return (dx if ng[0] else None), ggamma, gbeta, None, None, None, gsv, gmean, gnoise, None, None, None
-
-
-class _EpisodeLaplaceBnFn(torch.autograd.Function):
-    """Bernoulli-likelihood training episode straight from the trunk output X (N <= 127): the front end of `_EpisodeLossBnFn` (statistics + Gram in one pass,
-    the normalised features never written) -> mode, lml, dE -> backward dkt_gram_bn_bwd_f32, which takes dE exactly as it takes the Gaussian W."""
+    def de(saved):
+        w, *_ = saved
+        return w
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps, use_bn, y, sv, cls_weight, max_iter):
-        d = x.shape[2]
-        if use_bn and os.environ.get("DKT_FUSED_STATS", "1") != "0":
+    def backward(saved, shapes, gobj, need_y, need_sv, need_mean, need_noise, *_):
+        *_, dsv, dmean, dnoise, cw = saved
+        return (None,) + hyper_grads(gobj, cw, dsv if need_sv else None, dmean if need_mean else None, dnoise if need_noise else None, shapes) + (None, None, None)
+
+
+class _FeatureSpaceGaussian(_Gaussian):
+    """The same objective for the linear kernels in feature space (D <= 64 < N), on the rows Z and not on E:
+       A = Z^T Z, P = Z^T (Y - m) (dkt_lowrank_gram_f32) -> the D x D model K'_c = sv_c A + noise_c I through dkt_mll_f32 (jitter ladder and all)
+       -> alpha, logp, hyper-parameter gradients, V (dkt_lowrank_finish_f32); dZ = g_b (V^T T + 2 Z W') (dkt_lowrank_bwd_f32) from (v, t, wd) in the place of W.
+    Neither E[B,N,N] nor W[B,N,N] is ever formed (reference lines replaced: methods/DKT.py:375-378, 161-163)."""
+    on_features = True
+    de = None
+
+    @staticmethod
+    def forward(rows, y, sv, mean, noise, cls_weight, jitter0, max_tries):
+        z, unit_rows = rows
+        cw_ = _req(cls_weight.reshape(-1), "cls_weight", 1)
+        o = _lowrank_forward(z, _req(y, "y"), _req(sv.reshape(-1), "sv", 1), _req(mean.reshape(-1), "mean", 1), _req(noise.reshape(-1), "noise", 1), cw_,
+                             jitter0, max_tries, unit_rows)
+        return (o["obj"], (o["logp"], o["alpha"], o["info"], o["jitter"]), (o["v"], o["t"], o["wd"], o["dsv"], o["dmean"], o["dnoise"], cw_),
+                (sv.shape, mean.shape, noise.shape))
+
+    @staticmethod
+    def drows(z, saved, gobj):
+        v, t, wd, *_ = saved
+        return _lowrank_backward(z, v, t, wd, gobj)
+
+
+class _Laplace:
+    """Bernoulli likelihood, K_c = sv_c E: the mode without autograd, then lml, dE and the parts of d sv at the mode (`_laplace_forward`).  Outputs (lml, iters).
+    Episodes of up to 127 rows: behind the BN trunk front end it takes the resident form only."""
+    on_features, resident_only = False, True
+
+    @staticmethod
+    def forward(e, y, sv, cls_weight, max_iter):
+        obj, lml, iters, dk, dscale = _laplace_forward(e, y, cls_weight, sv, max_iter)
+        return obj, (lml, iters), (dk, dscale), None if sv is None else sv.shape
+
+    @staticmethod
+    def de(saved):
+        dk, _ = saved
+        return dk
+
+    @staticmethod
+    def backward(saved, sv_shape, gobj, need_y, need_sv, *_):
+        _, dscale = saved
+        return None, (_sum_episodes(gobj, dscale, sv_shape) if need_sv else None), None, None
+
+
+def _rows_grad(objv, osaved, z, gobj, unit_rows):
+    """dZ of E = Z Z^T with the upstream gradient folded in as ep_scale: g_b (dE + dE^T) Z (dkt_gram_bwd_f32; dE is symmetric as dkt_mll_f32 and
+    dkt_laplace_grad_f32 write it), or what the feature-space objective makes of the rows itself."""
+    if objv.on_features:
+        return objv.drows(z, osaved, gobj)
+    return gram_bwd(objv.de(osaved), z, gobj, unit_rows=unit_rows, w_symmetric=True)
+
+
+class _GivenE:
+    """E is an argument; its gradient is grad_out * dE.  No output of its own."""
+    nargs = 1
+
+    @staticmethod
+    def forward(objv, e):
+        return e, (), (), None
+
+    @staticmethod
+    def backward(saved, static, objv, osaved, gobj, need_e):
+        de = objv.de(osaved)                                                      # [B,N,N] or [B,C,N,N] (per-class E)
+        return (de * gobj.reshape([-1] + [1] * (de.dim() - 1)) if need_e else None,)
+
+
+class _LinearGram:
+    """linear / cossim / bncossim: E = Z Z^T (dkt_gram_f32); the feature-space objective takes Z itself and E is None.  Output E."""
+    nargs = 2
+
+    @staticmethod
+    def forward(objv, z, unit_rows):
+        unit_rows = bool(unit_rows)
+        if objv.on_features:
+            z = _req(z, "z", 3)
+            return (z, unit_rows), (None,), (z,), unit_rows
+        e = gram(z, None, KERNEL_LINEAR_UNIT if unit_rows else KERNEL_LINEAR)
+        return e, (e,), (z,), unit_rows
+
+    @staticmethod
+    def backward(saved, unit_rows, objv, osaved, gobj, need_z, *_):
+        z, = saved
+        return (_rows_grad(objv, osaved, z, gobj, unit_rows) if need_z else None), None
+
+
+class _ClassKernel:
+    """The kernels whose class models own a base-kernel parameter (rbf / matern: lengthscale [C]; poli1 / poli2: offset [C]; reference DKT.py:63-66, 352-365):
+    ONE contraction per episode (dkt_gram_f32: squared distances or Gram) -> the C class kernels E [B,C,N,N] (dkt_class_kernel_f32); backward
+    dkt_class_kernel_bwd_f32 (sum over the classes, parameter gradients) -> dkt_gram_bwd_f32 (upstream grad as ep_scale).  Output E."""
+    nargs = 5
+
+    @staticmethod
+    def forward(objv, z, param, cmap, power, base_kind):
+        one = torch.ones(1, device=z.device, dtype=torch.float32)
+        base = gram(z, None, base_kind, one if base_kind == KERNEL_SQDIST else None)
+        e = class_kernel(base, cmap, power, param)
+        return e, (e,), (z, base, param), (int(cmap), int(power))
+
+    @staticmethod
+    def backward(saved, maps, objv, osaved, gobj, need_z, need_param, *_):
+        z, base, param = saved
+        dz = gparam = None
+        if need_z or need_param:
+            wp, dpar = class_kernel_bwd(objv.de(osaved), base, maps[0], maps[1], param)
+            if need_z:
+                dz = gram_bwd(wp, z, gobj)
+            if need_param:
+                gparam = _sum_episodes(gobj, dpar, param.shape)
+        return dz, gparam, None, None, None
+
+
+class _BnTrunk:
+    """Straight from the trunk output X: [BatchNorm1d(train) +] F.normalize + linear Gram.  use_bn=False is the plain cossim kernel (no bn_out: affine map = identity).
+    Up to 128 rows, resident: dkt_gram_bn_train_f32 (statistics + Gram in one pass over x; DKT_FUSED_STATS=0: dkt_bn_stats_f32 + dkt_gram_bn_f32), backward
+    dkt_gram_bn_bwd_f32, which takes the Laplace dE exactly as it takes the Gaussian W; the normalised features are never written to memory.
+    More than 128 rows (the 20-way shapes) or the feature-space objective, big: dkt_bn_stats_f32 -> dkt_affine_normalize_f32 (Zn written once: the large-N Gram
+    kernels take unit rows as input) -> dkt_gram_f32, or no E at all in feature space (D <= 64 < N, Conv4S / Omniglot: csrc/dkt_lowrank.hip); backward
+    dkt_gram_bwd_f32 / dkt_lowrank_bwd_f32 -> dkt_normalize_bn_bwd_f32.
+    X in bfloat16 / float16 (a mixed-precision backbone): the same route through the *_x16 twins of the front-end calls; the gradient of X comes back
+    in X's dtype, everything behind the front end (Zn, E, the objective, the hyper-parameter and BatchNorm gradients) is fp32.
+    Outputs E (None in feature space), batch_mean, batch_var_unbiased, a, s, rnorm."""
+    nargs = 5
+
+    @staticmethod
+    def forward(objv, x, gamma, beta, eps, use_bn):
+        use_bn = bool(use_bn)
+        n, d = x.shape[1], x.shape[2]
+        big = objv.on_features or (n > FUSED_EP_MAX_N and not objv.resident_only)
+        e = zn = None
+        if use_bn and not big and os.environ.get("DKT_FUSED_STATS", "1") != "0":
             e, rnorm, st = gram_bn_train(x, gamma, beta, eps)               # statistics + Gram in one pass over x
+        elif use_bn:
+            st = bn_stats(x, gamma, beta, eps)
+        if use_bn:
             a, s, bmean, rstd, bvar = st["a"], st["s"], st["mean"], st["rstd"], st["var_unbiased"]
         else:
-            if use_bn:
-                st = bn_stats(x, gamma, beta, eps)
-                a, s, bmean, rstd, bvar = st["a"], st["s"], st["mean"], st["rstd"], st["var_unbiased"]
-            else:
-                a = torch.ones(d, device=x.device, dtype=torch.float32)
-                s = torch.zeros(d, device=x.device, dtype=torch.float32)
-                bmean = rstd = bvar = torch.zeros(0, device=x.device, dtype=torch.float32)
+            a = torch.ones(d, device=x.device, dtype=torch.float32)
+            s = torch.zeros(d, device=x.device, dtype=torch.float32)
+            bmean = rstd = bvar = torch.zeros(0, device=x.device, dtype=torch.float32)
+        static = (use_bn, None if gamma is None else gamma.shape, None if beta is None else beta.shape)
+        if big:
+            zn, rnorm = affine_normalize(x, a, s)
+            if objv.on_features:
+                return (zn, True), (None, bmean, bvar, a, s, rnorm), (x, a, s, bmean, rstd, rnorm, None, zn), static
+            e = gram(zn, None, KERNEL_LINEAR_UNIT)
+            return e, (e, bmean, bvar, a, s, rnorm), (x, a, s, bmean, rstd, rnorm, None, zn), static
+        if e is None:
             e, rnorm = gram_bn(x, a, s)
-        obj, lml, iters, dk, dscale = _laplace_forward(e, y, cls_weight, sv.detach(), max_iter)
-        ctx.use_bn = bool(use_bn)
-        ctx.save_for_backward(x, e, dk, a, s, bmean, rstd, rnorm, dscale)
-        ctx.shapes = (sv.shape, None if gamma is None else gamma.shape, None if beta is None else beta.shape)
-        ctx.mark_non_differentiable(lml, iters, e, bmean, bvar, a, s, rnorm)
-        ctx.set_materialize_grads(False)
-        return obj, lml, iters, e, bmean, bvar, a, s, rnorm
+        return e, (e, bmean, bvar, a, s, rnorm), (x, a, s, bmean, rstd, rnorm, e, None), static
+
+    @staticmethod
+    def backward(saved, static, objv, osaved, gobj, need_x, need_gamma, need_beta, *_):
+        x, a, s, bmean, rstd, rnorm, e, zn = saved                                 # resident: E, no Zn; big: Zn, and E is not kept
+        use_bn, gamma_shape, beta_shape = static
+        if not use_bn:
+            bmean = rstd = None
+        if zn is not None:
+            dx, dg, db = normalize_bn_bwd(_rows_grad(objv, osaved, zn, gobj, True), zn, x, a, rnorm, bmean, rstd)
+        else:
+            dx, dg, db = gram_bn_bwd(objv.de(osaved), e, x, a, s, rnorm, bmean, rstd, gobj)
+        ggamma = gbeta = None
+        if dg is not None and (need_gamma or need_beta):
+            sg, sb = bn_param_grads(dg, db)
+            ggamma = sg.reshape(gamma_shape) if need_gamma else None
+            gbeta = sb.reshape(beta_shape) if need_beta else None
+        return (dx if need_x else None), ggamma, gbeta, None, None
+
+
+class _EpisodeFn(torch.autograd.Function):
+    """obj [B] of a (front end, objective) pair and, behind it, the objective's outputs and the front end's, all non-differentiable.  The arguments are the
+    front end's, then the objective's (the signatures of their `forward`s)."""
+
+    @staticmethod
+    def forward(ctx, front, objv, *args):
+        n = front.nargs
+        m, outs, saved, static = front.forward(objv, *args[:n])
+        obj, aux, osaved, ostatic = objv.forward(m, *args[n:])
+        ctx.save_for_backward(*saved, *osaved)
+        ctx.episode = (front, objv, len(saved), static, ostatic)
+        outs = aux + outs
+        ctx.mark_non_differentiable(*[o for o in outs if o is not None])
+        ctx.set_materialize_grads(False)       # (otherwise autograd zero-fills a gradient tensor for every non-differentiable output: E alone is 361 MB at cfg2)
+        return (obj,) + outs
 
     @staticmethod
     def backward(ctx, gobj, *_unused):
+        need = ctx.needs_input_grad
         if gobj is None:
-            return (None,) * 9
-        x, e, dk, a, s, bmean, rstd, rnorm, dscale = ctx.saved_tensors
+            return (None,) * len(need)
+        front, objv, nsaved, static, ostatic = ctx.episode
+        saved = ctx.saved_tensors
+        osaved = saved[nsaved:]
         gobj = gobj.contiguous()
-        dx, dg, db = gram_bn_bwd(dk, e, x, a, s, rnorm, bmean if ctx.use_bn else None, rstd if ctx.use_bn else None, gobj)
-        ng = ctx.needs_input_grad
-        ggamma = gbeta = None
-        if dg is not None and ((ng[1] and ctx.shapes[1] is not None) or (ng[2] and ctx.shapes[2] is not None)):
-            sg, sb = bn_param_grads(dg, db)
-            ggamma = sg.reshape(ctx.shapes[1]) if (ng[1] and ctx.shapes[1] is not None) else None
-            gbeta = sb.reshape(ctx.shapes[2]) if (ng[2] and ctx.shapes[2] is not None) else None
-        gsv = (gobj.reshape(-1, 1) * dscale).sum(0).reshape(ctx.shapes[0]) if ng[6] else None
-        return (dx if ng[0] else None), ggamma, gbeta, None, None, None, gsv, None, None
+        n = 2 + front.nargs                                                        # (front, objv) come first
+        return ((None, None) + front.backward(saved[:nsaved], static, objv, osaved, gobj, *need[2:n])
+                + objv.backward(osaved, ostatic, gobj, *need[n:]))
+
+
+def mll_objective(e, y, sv, mean, noise, cls_weight, jitter0: float = 1e-6, max_tries: int = 3):
+    """Returns (obj[B], logp[B,C], alpha[B,C,N], info[B,C], jitter[B,C])."""
+    return _EpisodeFn.apply(_GivenE, _Gaussian, e, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+
+
+def laplace_objective(K, Y, cls_weight, scale=None, max_iter: int = 100):
+    """Differentiable (in K and scale) Laplace training objective of B episodes: returns (obj [B], lml [B,C], iters [B,C]); arguments as `laplace_grad`.
+    Forward: `laplace_mode` without autograd, then `laplace_grad`; no host read-back (graph-capturable like the other episode calls)."""
+    return _EpisodeFn.apply(_GivenE, _Laplace, K, Y, scale, cls_weight, max_iter)
+
+
+def episode_loss_laplace(z, y, sv, cls_weight, kernel: str, lengthscale=None, offset=None, unit_rows: bool = False, max_iter: int = 100):
+    """Bernoulli-likelihood training episode(s) z [B,N,D] (N <= 127, C <= 32), y in {0,1}: K_c = sv_c * k_c(z, z).  Returns (obj [B], lml [B,C], iters [B,C], E)."""
+    z = _req(z, "z", 3)
+    if kernel in LINEAR_KINDS:
+        return _EpisodeFn.apply(_LinearGram, _Laplace, z, unit_rows, y, sv, cls_weight, max_iter)
+    cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
+    return _EpisodeFn.apply(_ClassKernel, _Laplace, z, param, cmap, power, base_kind, y, sv, cls_weight, max_iter)
 
 
 def episode_loss_laplace_bn(x, gamma, beta, y, sv, cls_weight, eps: float = 1e-5, use_bn: bool = True, max_iter: int = 100):
     """x [B,N,D] trunk output BEFORE bn_out, N <= 127.  Returns (obj [B], lml, iters, E, batch_mean, batch_var_unbiased, a, s, rnorm)."""
-    return _EpisodeLaplaceBnFn.apply(x, gamma, beta, eps, use_bn, y, sv, cls_weight, max_iter)
+    return _EpisodeFn.apply(_BnTrunk, _Laplace, x, gamma, beta, eps, use_bn, y, sv, cls_weight, max_iter)
+
+
+def episode_loss_class_kernel(z, y, sv, mean, noise, cls_weight, kernel: str, lengthscale=None, offset=None,
+                              jitter0: float = 1e-6, max_tries: int = 3):
+    """Training episode(s) z:[B,N,D] for rbf / matern / poli1 / poli2 with per-class lengthscale / offset [C], sizes of
+    mll_per_class_supported().
+    Returns (obj[B], logp[B,C], alpha[B,C,N], info[B,C], jitter[B,C], E[B,C,N,N])."""
+    cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
+    return _EpisodeFn.apply(_ClassKernel, _Gaussian, _req(z, "z", 3), param, cmap, power, base_kind, y, sv, mean, noise, cls_weight, jitter0, max_tries)
 
 
 def episode_loss_bn(x, gamma, beta, y, sv, mean, noise, cls_weight, eps: float = 1e-5, jitter0: float = 1e-6, max_tries: int = 3,
@@ -1451,7 +1358,8 @@ def episode_loss_bn(x, gamma, beta, y, sv, mean, noise, cls_weight, eps: float =
     """x:[B,N,D] trunk output BEFORE bn_out (float32, bfloat16 or float16).  Returns (obj[B], logp, alpha, info, jitter, E (None when the episode ran in feature space: lowrank_applies), batch_mean[B,D],
     batch_var_unbiased[B,D]) -- the last two feed the caller's running-statistics update -- plus, with full=True, the folded
     affine map a, s and the row scales rnorm (zn = (a x + s) rnorm: what a caller needs to re-create the normalised features)."""
-    out = _EpisodeLossBnFn.apply(x, gamma, beta, eps, use_bn, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+    objv = _FeatureSpaceGaussian if lowrank_applies(x.shape[1], x.shape[2], y.shape[-2], x.shape[0], front_end=True) else _Gaussian
+    out = _EpisodeFn.apply(_BnTrunk, objv, x, gamma, beta, eps, use_bn, y, sv, mean, noise, cls_weight, jitter0, max_tries)
     return out if full else out[:8]
 
 
@@ -1461,6 +1369,5 @@ def episode_loss_linear(z, y, sv, mean, noise, cls_weight, jitter0: float = 1e-6
     the scaled 2-way f16 split (same fp32-level accuracy, less staging work).
     D <= 64 < N where it wins (lowrank_applies: the Conv4S / Omniglot episodes -- every 420-row batch, 105-row batches from 3072 episodes): the episode runs in
     feature space and E is None -- no N x N matrix exists."""
-    if z.dim() == 3 and lowrank_applies(z.shape[1], z.shape[2], y.shape[-2], z.shape[0]):
-        return _EpisodeLossLowRankFn.apply(z, y, sv, mean, noise, cls_weight, jitter0, max_tries, bool(unit_rows)) + (None,)
-    return _EpisodeLossLinearFn.apply(z, y, sv, mean, noise, cls_weight, jitter0, max_tries, unit_rows)
+    objv = _FeatureSpaceGaussian if z.dim() == 3 and lowrank_applies(z.shape[1], z.shape[2], y.shape[-2], z.shape[0]) else _Gaussian
+    return _EpisodeFn.apply(_LinearGram, objv, z, unit_rows, y, sv, mean, noise, cls_weight, jitter0, max_tries)
