@@ -98,6 +98,39 @@ def _autocast_active(amp) -> bool:
     return amp is not None or torch.is_autocast_enabled("cuda")
 
 
+def _set_amp(self, value):
+    object.__setattr__(self, "_amp", amp_mode(value))
+
+
+amp_property = property(lambda self: self._amp, _set_amp)      # `amp` of the classification and the regression models: validated on assignment
+
+
+def _not_pd(where, note=""):
+    raise RuntimeError("%s: kernel matrix not positive definite after jitter retries%s" % (where, note))
+
+
+# dkt_class_kernel_bwd_f32 takes up to 32 class maps per launch: the `c <= 32` of ops.mll_per_class_supported
+CLASS_GROUP = 32
+
+
+def _class_plan(n, c):
+    """How a call over the C class models of an N-row episode is split: (class slices, class-kernel form).  Up to 447 rows the class-kernel form
+    (one contraction, the class maps and ONE marginal-likelihood launch per slice): one slice `None` = every class, nothing is cut, or groups of
+    CLASS_GROUP classes; N + 1 > 448: the single-model form, one Gram + one launch per class (the blocked path serves those sizes)."""
+    if not ops.mll_per_class_supported(n, 1):
+        return [slice(k, k + 1) for k in range(c)], False
+    if ops.mll_per_class_supported(n, c):
+        return [None], True
+    return [slice(k, k + CLASS_GROUP) for k in range(0, c, CLASS_GROUP)], True
+
+
+def _class_cut(s, y, *per_class):
+    """The targets y [.., C, N] and the per-class vectors (None stays None) of the class slice s."""
+    if s is None:
+        return (y,) + per_class
+    return (y[..., s, :].contiguous(),) + tuple(None if t is None else t[s] for t in per_class)
+
+
 class _FusableBatchNorm1d(nn.BatchNorm1d):
     """bn_out (DKT.py:48) with the same parameters / buffers / state-dict keys as nn.BatchNorm1d; `bypass` lets the fused
     front end (ops.episode_loss_bn) take the trunk output in front of it and run the normalisation inside the Gram kernels."""
@@ -212,13 +245,7 @@ class DKT(MetaTemplate):
         # predicts with it
         self.laplace = "deep" if self.likelihood_type == "bernoulli" else False
 
-    @property
-    def amp(self):
-        return self._amp
-
-    @amp.setter
-    def amp(self, value):
-        object.__setattr__(self, "_amp", amp_mode(value))
+    amp = amp_property
 
     # ------------------------------------------------------------------ construction
     def init_summary(self):
@@ -299,7 +326,7 @@ class DKT(MetaTemplate):
             return z
         # mixed precision: the backbone under autocast, then ONE conversion to fp32 at the head boundary and bn_out / F.normalize in fp32
         z = self._trunk_features(x)
-        bn = getattr(self.feature_extractor.trunk, "bn_out", None)
+        bn = self._bn_out()
         with torch.autocast("cuda", enabled=False):
             z = z.float()
             if bn is not None:
@@ -312,10 +339,30 @@ class DKT(MetaTemplate):
         m = self.model
         return m.scale_times_variance(), m.mean, m.noise
 
+    def _hypers_detached(self):
+        """(sv, mean, noise, lengthscale, offset) outside autograd, lengthscale / offset None where the kernel has none: what every prediction path reads."""
+        m = self.model
+        ls, off = m.lengthscale, m.offset
+        return (m.scale_times_variance().detach(), m.mean.detach(), m.noise.detach(),
+                None if ls is None else ls.detach(), None if off is None else off.detach())
+
+    def _mode(self, train, features=None):
+        """Train / eval mode of the GP side (model, likelihood) and of the backbone (`features`; None: the same as the GP side)."""
+        self.model.train(train)
+        self.likelihood.train(train)
+        self.feature_extractor.train(train if features is None else features)
+
+    def _bn_out(self, fused=False):
+        """The trunk's bn_out, or None.  fused=True (the two fused front ends): only the bn_out this class appended for "bncossim" is folded into the
+        Gram kernels, any other kernel type runs them without one; the torch paths apply or bypass whatever bn_out the trunk carries."""
+        if fused and self.kernel_type != "bncossim":
+            return None
+        return getattr(self.feature_extractor.trunk, "bn_out", None)
+
     # ---- fused front end: bn_out + F.normalize folded into the Gram kernels (ops.episode_loss_bn) ----
     def _trunk_features(self, x):
         """Backbone output BEFORE bn_out (the module the reference appends to the trunk at DKT.py:48)."""
-        bn = getattr(self.feature_extractor.trunk, "bn_out", None)
+        bn = self._bn_out()
         with backbone_autocast(self.amp):
             if bn is None:
                 return self.feature_extractor.forward(x)
@@ -342,7 +389,7 @@ class DKT(MetaTemplate):
         c = y.shape[-2]
         sv, mean, noise = self._hypers()
         cw = torch.full((c,), -1.0 / (c * n), device=xb.device, dtype=torch.float32)
-        bn = getattr(self.feature_extractor.trunk, "bn_out", None) if self.kernel_type == "bncossim" else None
+        bn = self._bn_out(True)
         if self.likelihood_type == "bernoulli":
             self._check_bernoulli_rows(n, c)
             obj, logp, iters, e, bmean, bvar, a, s, rnorm = ops.episode_loss_laplace_bn(
@@ -359,28 +406,34 @@ class DKT(MetaTemplate):
             obj, logp, alpha, info, jit, e, bmean, bvar, a, s, rnorm = outs
         with torch.no_grad():
             if bn is not None and bn.track_running_stats:
-                mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked.item() + 1)
-                nb = xb.shape[0]
-                if bn.momentum is None and nb > 1:
-                    # cumulative moving average: the factor changes with every episode, 1 / (num_batches_tracked + 1) -- the episodes one by one
-                    nbt = int(bn.num_batches_tracked.item())
-                    for bi in range(nb):
-                        f_ = 1.0 / float(nbt + bi + 1)
-                        bn.running_mean.mul_(1.0 - f_).add_(bmean[bi], alpha=f_)
-                        bn.running_var.mul_(1.0 - f_).add_(bvar[bi], alpha=f_)
-                elif nb == 1:
-                    bn.running_mean.mul_(1.0 - mom).add_(bmean[0], alpha=mom)
-                    bn.running_var.mul_(1.0 - mom).add_(bvar[0], alpha=mom)
-                else:       # nb sequential momentum updates in closed form: r <- (1-m)^nb r + m sum_b (1-m)^(nb-1-b) x_b
-                    wts = mom * (1.0 - mom) ** torch.arange(nb - 1, -1, -1, device=xb.device, dtype=torch.float32)
-                    bn.running_mean.mul_((1.0 - mom) ** nb).add_((bmean * wts[:, None]).sum(0))
-                    bn.running_var.mul_((1.0 - mom) ** nb).add_((bvar * wts[:, None]).sum(0))
-                bn.num_batches_tracked += nb
+                self._update_running_stats(bn, bmean, bvar)
             z_train = None
             if want_z:
                 z_train = (xb[0].detach() * a.reshape(-1, xb.shape[2])[0] + s.reshape(-1, xb.shape[2])[0]) * rnorm[0].unsqueeze(1)
         aux = dict(logp=logp, alpha=alpha, info=info, jitter=jit, e=None if e is None else e.detach())
         return obj.mean(), aux, z_train
+
+    @staticmethod
+    def _update_running_stats(bn, bmean, bvar):
+        """bn_out's running estimates after the nb episodes whose batch statistics are bmean / bvar [nb, D], exactly as nn.BatchNorm1d would leave them
+        after seeing the episodes one by one (called under torch.no_grad)."""
+        mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked.item() + 1)
+        nb = bmean.shape[0]
+        if bn.momentum is None and nb > 1:
+            # cumulative moving average: the factor changes with every episode, 1 / (num_batches_tracked + 1) -- the episodes one by one
+            nbt = int(bn.num_batches_tracked.item())
+            for bi in range(nb):
+                f_ = 1.0 / float(nbt + bi + 1)
+                bn.running_mean.mul_(1.0 - f_).add_(bmean[bi], alpha=f_)
+                bn.running_var.mul_(1.0 - f_).add_(bvar[bi], alpha=f_)
+        elif nb == 1:
+            bn.running_mean.mul_(1.0 - mom).add_(bmean[0], alpha=mom)
+            bn.running_var.mul_(1.0 - mom).add_(bvar[0], alpha=mom)
+        else:       # nb sequential momentum updates in closed form: r <- (1-m)^nb r + m sum_b (1-m)^(nb-1-b) x_b
+            wts = mom * (1.0 - mom) ** torch.arange(nb - 1, -1, -1, device=bmean.device, dtype=torch.float32)
+            bn.running_mean.mul_((1.0 - mom) ** nb).add_((bmean * wts[:, None]).sum(0))
+            bn.running_var.mul_((1.0 - mom) ** nb).add_((bvar * wts[:, None]).sum(0))
+        bn.num_batches_tracked += nb
 
     @gp_head
     def _episode_loss(self, z, y):
@@ -405,42 +458,32 @@ class DKT(MetaTemplate):
             # rbf / matern / polynomial: every class model owns its lengthscale / offset (one ExactGPLayer per class,
             # DKT.py:63-66), so the base matrix differs per class
             ls, off = self.model.lengthscale, self.model.offset
-            if ops.mll_per_class_supported(n, c):
-                # ONE contraction per episode (squared distances / Gram), the C class maps in one launch, ONE marginal-likelihood
-                # launch over all (episode, class) matrices (DKT_MLL_E_PER_CLASS), the chain rule back in two launches
-                obj, logp, alpha, info, jit, e = ops.episode_loss_class_kernel(zb, y, sv, mean, noise, cw, self.kernel_type, ls, off,
-                                                                               self.jitter0, self.max_tries)
-            elif ops.mll_per_class_supported(n, 1):
-                # more than 32 classes (dkt_class_kernel_bwd_f32 takes up to 32 class maps per launch): the same one-launch path per GROUP of 32 classes --
-                # ceil(C / 32) groups instead of C single-model calls; the class weights already carry 1 / (C N), so the groups' objectives add up
-                parts = [ops.episode_loss_class_kernel(zb, y[..., k:k + 32, :].contiguous(), sv[k:k + 32], mean[k:k + 32], noise[k:k + 32], cw[k:k + 32],
-                                                       self.kernel_type, None if ls is None else ls[k:k + 32], None if off is None else off[k:k + 32],
-                                                       self.jitter0, self.max_tries) for k in range(0, c, 32)]
+            groups, class_form = _class_plan(n, c)
+            parts = []
+            for s in groups:
+                yk, svk, meank, noisek, cwk, lsk, offk = _class_cut(s, y, sv, mean, noise, cw, ls, off)
+                if class_form:
+                    # ONE contraction per episode (squared distances / Gram), the class maps in one launch, ONE marginal-likelihood
+                    # launch over all (episode, class) matrices (DKT_MLL_E_PER_CLASS), the chain rule back in two launches
+                    parts.append(ops.episode_loss_class_kernel(zb, yk, svk, meank, noisek, cwk, self.kernel_type, lsk, offk, self.jitter0, self.max_tries))
+                else:       # (E of a single model is not kept: nothing reads it)
+                    parts.append(ops.mll_objective(ops.base_matrix(zb, self.kernel_type, lsk, offk), yk, svk, meank, noisek, cwk,
+                                                   self.jitter0, self.max_tries) + (None,))
+            if len(parts) == 1:
+                obj, logp, alpha, info, jit, e = parts[0]
+            else:           # the class weights already carry 1 / (C N), so the parts' objectives add up
                 obj = torch.stack([pt[0] for pt in parts], 0).sum(0)
-                logp, alpha, info, jit, e = (torch.cat([pt[i] for pt in parts], 1) for i in range(1, 6))
-            else:
-                # N > 447: one Gram + one single-model launch per class (the blocked path serves those sizes)
-                objs, logps, alphas, infos, jits = [], [], [], [], []
-                for k in range(c):
-                    e = ops.base_matrix(zb, self.kernel_type, None if ls is None else ls[k:k + 1], None if off is None else off[k:k + 1])
-                    yk = y[..., k:k + 1, :].contiguous()
-                    o, lp, al, inf, jt = ops.mll_objective(e, yk, sv[k:k + 1], mean[k:k + 1], noise[k:k + 1], cw[k:k + 1], self.jitter0, self.max_tries)
-                    objs.append(o); logps.append(lp); alphas.append(al); infos.append(inf); jits.append(jt)
-                obj = torch.stack(objs, 0).sum(0)
-                logp, alpha, info, jit = torch.cat(logps, 1), torch.cat(alphas, 1), torch.cat(infos, 1), torch.cat(jits, 1)
+                logp, alpha, info, jit = (torch.cat([pt[i] for pt in parts], 1) for i in range(1, 5))
+                e = torch.cat([pt[5] for pt in parts], 1) if class_form else None
         aux = dict(logp=logp, alpha=alpha, info=info, jitter=jit, e=None if e is None else e.detach())
         return obj.mean(), aux
 
     @gp_head
     def _posterior(self, z_cond, y, z_star, e_cond=None):
         """Mean cache on the conditioning set, posterior means [C,M] and labels [M] at z_star."""
-        sv, mean, noise = self._hypers()
-        ls, off = self.model.lengthscale, self.model.offset
-        ls = None if ls is None else ls.detach()
-        off = None if off is None else off.detach()
+        sv, mean, noise, ls, off = self._hypers_detached()
         zc = z_cond.detach().unsqueeze(0)
         zs = z_star.detach().unsqueeze(0)
-        sv, mean, noise = sv.detach(), mean.detach(), noise.detach()
         if self.kernel_type in LINEAR_KINDS:
             if e_cond is None:
                 e_cond = ops.kernel_matrix(zc, None, self.kernel_type)
@@ -448,29 +491,18 @@ class DKT(MetaTemplate):
             mu, labels = ops.predict(ops.kernel_matrix(zs, zc, self.kernel_type), out["alpha"], sv, mean)
             return mu[0], labels[0], out
         # per-class base matrices (E depends on the class model's own, post-step, lengthscale / offset)
-        if ops.mll_per_class_supported(zc.shape[1], y.shape[-2]):
-            # one contraction for the conditioning set, one for the cross kernel; the class maps element-wise; one launch for all classes
-            e_c = ops.kernel_matrix_per_class(zc, None, self.kernel_type, ls, off)               # [1, C, N, N]
-            out = ops.mll(e_c, y, sv, mean, noise, jitter0=self.jitter0, max_tries=self.max_tries)
-            ex_c = ops.kernel_matrix_per_class(zs, zc, self.kernel_type, ls, off)                # [1, C, M, N]
-            mu, labels = ops.predict(ex_c, out["alpha"], sv, mean)                               # dkt_predict_per_class_f32
-            return mu[0], labels[0], {key: out[key] for key in ("logp", "alpha", "jitter", "info")}
+        # class-kernel form: one contraction for the conditioning set, one for the cross kernel, the class maps element-wise ([1, C, N, N], [1, C, M, N]), one
+        # marginal-likelihood launch and one dkt_predict_per_class_f32 launch per class slice; single-model form: the same four calls per class
+        groups, class_form = _class_plan(zc.shape[1], y.shape[-2])
+        kmat = ops.kernel_matrix_per_class if class_form else ops.kernel_matrix
         mus, outs = [], []
-        if ops.mll_per_class_supported(zc.shape[1], 1):
-            # more than 32 classes: the one-launch path per group of 32 classes
-            for k in range(0, y.shape[-2], 32):
-                lk, ok = (None if ls is None else ls[k:k + 32]), (None if off is None else off[k:k + 32])
-                o = ops.mll(ops.kernel_matrix_per_class(zc, None, self.kernel_type, lk, ok), y[..., k:k + 32, :].contiguous(), sv[k:k + 32], mean[k:k + 32],
-                            noise[k:k + 32], jitter0=self.jitter0, max_tries=self.max_tries)
-                m, _ = ops.predict(ops.kernel_matrix_per_class(zs, zc, self.kernel_type, lk, ok), o["alpha"], sv[k:k + 32], mean[k:k + 32], want_labels=False)
-                mus.append(m); outs.append(o)
-        else:
-            for k in range(y.shape[-2]):                     # N > 447: one single-model call per class
-                lk, ok = (None if ls is None else ls[k:k + 1]), (None if off is None else off[k:k + 1])
-                o = ops.mll(ops.kernel_matrix(zc, None, self.kernel_type, lk, ok), y[..., k:k + 1, :].contiguous(), sv[k:k + 1], mean[k:k + 1],
-                            noise[k:k + 1], jitter0=self.jitter0, max_tries=self.max_tries)
-                m, _ = ops.predict(ops.kernel_matrix(zs, zc, self.kernel_type, lk, ok), o["alpha"], sv[k:k + 1], mean[k:k + 1], want_labels=False)
-                mus.append(m); outs.append(o)
+        for s in groups:
+            yk, svk, meank, noisek, lsk, offk = _class_cut(s, y, sv, mean, noise, ls, off)
+            o = ops.mll(kmat(zc, None, self.kernel_type, lsk, offk), yk, svk, meank, noisek, jitter0=self.jitter0, max_tries=self.max_tries)
+            m, labels = ops.predict(kmat(zs, zc, self.kernel_type, lsk, offk), o["alpha"], svk, meank, want_labels=len(groups) == 1)
+            mus.append(m); outs.append(o)
+        if len(groups) == 1:                                 # (the labels come from the predict kernel)
+            return m[0], labels[0], {key: o[key] for key in ("logp", "alpha", "jitter", "info")}
         mu = torch.cat(mus, 1)
         out = {key: torch.cat([o[key] for o in outs], 1) for key in ("logp", "alpha", "jitter", "info")}
         # first maximum wins, as np.argmax (torch.argmax does not promise which of several equal maxima it returns on the GPU)
@@ -483,7 +515,7 @@ class DKT(MetaTemplate):
         stacked [support; query] trunk features (one backbone pass instead of two): E_all = Zn Zn^T, the conditioning matrix is
         its [:ns, :ns] block and the cross kernel its [ns:, :ns] block.  Returns None when the fused kernels do not apply."""
         ns, nq = x_support.shape[0], x_query.shape[0]
-        bn = getattr(self.feature_extractor.trunk, "bn_out", None) if self.kernel_type == "bncossim" else None
+        bn = self._bn_out(True)
         if self.feature_extractor.training or (bn is not None and not bn.track_running_stats):
             return None
         x_feat = self._trunk_features(torch.cat([x_support, x_query], 0)).detach()
@@ -506,17 +538,14 @@ class DKT(MetaTemplate):
         else:                                                 # (more than 128 rows: one normalisation kernel in front of the large-N Gram kernel)
             zn, _ = ops.affine_normalize(x_feat.unsqueeze(0).contiguous(), a.contiguous(), s.contiguous())
             e_all = ops.gram(zn, None, ops.KERNEL_LINEAR_UNIT)
-        sv, mean, noise = self._hypers()
-        out = ops.mll(e_all[:, :ns, :ns].contiguous(), y, sv.detach(), mean.detach(), noise.detach(), jitter0=self.jitter0,
-                      max_tries=self.max_tries)
-        mu, labels = ops.predict(e_all[:, ns:, :ns].contiguous(), out["alpha"], sv.detach(), mean.detach())
+        sv, mean, noise, _, _ = self._hypers_detached()
+        out = ops.mll(e_all[:, :ns, :ns].contiguous(), y, sv, mean, noise, jitter0=self.jitter0, max_tries=self.max_tries)
+        mu, labels = ops.predict(e_all[:, ns:, :ns].contiguous(), out["alpha"], sv, mean)
         return mu[0], labels[0], out
 
     def _train_forward(self, x_all, y_targets, nb, n_ep, want_z=True):
         """Forward of one training step from the uploaded images x_all:[nb * N, ch, H, W]: returns (loss, aux, z_train, fused)."""
-        self.model.train()
-        self.likelihood.train()
-        self.feature_extractor.train()
+        self._mode(True)
         # ONE backbone pass over the nb * N images of the step (meta-batch: the backbone's own BatchNorm2d layers then see
         # all of them as one batch, as any mini-batch training does; bn_out and the GPs stay per episode)
         x_feat = self._trunk_features(x_all)
@@ -533,7 +562,7 @@ class DKT(MetaTemplate):
             loss, aux, z_train = self._episode_loss_from_trunk(x_feat, y_targets, want_z=want_z)
             return loss, aux, z_train, True
         x_feat = x_feat.float()
-        bn = getattr(self.feature_extractor.trunk, "bn_out", None)        # torch bn_out / F.normalize in front of the Gram kernels
+        bn = self._bn_out()                                                 # torch bn_out / F.normalize in front of the Gram kernels
         if bn is None:
             z_train = x_feat
         elif nb == 1:
@@ -577,22 +606,28 @@ class DKT(MetaTemplate):
         return flag
 
     # ------------------------------------------------------------------ training
+    def _adam(self, **kwargs):
+        """The reference's two-group Adam (DKT.py:114): the GP hyper-parameters at 1e-4, the backbone at 1e-3."""
+        return torch.optim.Adam([{'params': self.model.parameters(), 'lr': 1e-4},
+                                 {'params': self.feature_extractor.parameters(), 'lr': 1e-3}], **kwargs)
+
+    def _check_bad_steps(self):
+        """Raises, on every rank alike, when a step since the start of the epoch failed (the accumulated device flag: ONE read-back)."""
+        if self._bad_steps is not None and float(self._bad_steps.item()) != 0.0:
+            _not_pd("DKT", " (GPyTorch raises NotPSDError here)")
+
     def train_loop(self, epoch, train_loader, optimizer, print_freq=10):
         # the optimizer argument is ignored and Adam re-created every call, as the reference does
         # (same update rule; on the GPU the fused implementation: one launch per parameter group instead of a dozen element-wise
         # ones, and it takes a device-side `found_inf` flag -- used below to SKIP the update of a step whose factorisation failed)
         fused_adam = os.environ.get("DKT_FUSED_ADAM", "1") == "1" and self.device.type == "cuda"
-        optimizer = torch.optim.Adam([{'params': self.model.parameters(), 'lr': 1e-4},
-                                      {'params': self.feature_extractor.parameters(), 'lr': 1e-3}], **({"fused": True} if fused_adam else {}))
         dev = self.device
         self._bad_steps = None
         # DKT_TRAIN_GRAPH=1: capture the per-episode step into a hipGraph (the loop is launch-bound: ~150 launches for ~1 ms of
         # GPU work).  Needs static shapes, no TensorBoard writer inside the step and a single process.
         use_graph = os.environ.get("DKT_TRAIN_GRAPH", "0") == "1" and not distributed.is_distributed()
         graph_step = None
-        if use_graph:
-            optimizer = torch.optim.Adam([{'params': self.model.parameters(), 'lr': 1e-4},
-                                          {'params': self.feature_extractor.parameters(), 'lr': 1e-3}], capturable=True)
+        optimizer = self._adam(capturable=True) if use_graph else self._adam(**({"fused": True} if fused_adam else {}))
         mb = max(1, int(getattr(self, "meta_batch", 1) or 1))
         if mb > 1:          # opt-in (train.py --meta_batch B): B episodes per Adam step; 1 = the reference's semantics (DKT.py:160-164)
             train_loader = _MetaBatched(train_loader, mb)
@@ -670,9 +705,7 @@ class DKT(MetaTemplate):
                 z_train = z_train[0].detach()
             e_first = None if aux["e"] is None else aux["e"][:1]      # (None: the episode ran in feature space, ops.lowrank_applies)
             with torch.no_grad():
-                self.model.eval()
-                self.likelihood.eval()
-                self.feature_extractor.eval()
+                self._mode(False)
                 z_eval = self._embed(x_all).detach().view(self.n_way, per, -1)
                 z_support = z_eval[:, :self.n_support].reshape(self.n_way * self.n_support, -1)
                 z_query = z_eval[:, self.n_support:].reshape(self.n_way * self.n_query, -1)
@@ -690,16 +723,12 @@ class DKT(MetaTemplate):
             if i % print_freq == 0:
                 if self.writer is not None:
                     self.writer.add_histogram('z_support', z_support, self.iteration)
-                if float(self._bad_steps.item()) != 0.0:
-                    raise RuntimeError("DKT: kernel matrix not positive definite after jitter retries "
-                                       "(GPyTorch raises NotPSDError here)")
+                self._check_bad_steps()
                 print('Epoch [{:d}] [{:d}/{:d}] | Outscale {:f} | Lenghtscale {:f} | Noise {:f} | Loss {:f} | Supp. {:f} | Query {:f}'.format(
                     epoch, i, len(train_loader), log_outputscale.item(), log_lengthscale.item(), log_noise.item(),
                     loss.item(), acc_support.item(), acc_query.item()))
         # failures after the last print point of the epoch (the flag is reset by the next call): raise here, on every rank alike
-        if self._bad_steps is not None and float(self._bad_steps.item()) != 0.0:
-            raise RuntimeError("DKT: kernel matrix not positive definite after jitter retries "
-                               "(GPyTorch raises NotPSDError here)")
+        self._check_bad_steps()
 
     # ------------------------------------------------------------------ evaluation
     def _upload(self, x):
@@ -735,13 +764,12 @@ class DKT(MetaTemplate):
         if kernel != "deep":
             raise ValueError("laplace kernel must be 'rbf0.1' or 'deep', got %r" % (kernel,))
         pick = slice(1, 2) if self.n_way == 2 else slice(None)
-        sv = self._hypers()[0].detach()[pick]
+        sv, _, _, ls, off = self._hypers_detached()
+        sv = sv[pick]
         if self.kernel_type in LINEAR_KINDS:
             e, ex = ops.kernel_matrix(zs, None, self.kernel_type).unsqueeze(1), ops.kernel_matrix(zq, zs, self.kernel_type).unsqueeze(1)
             exx = (zq * zq).sum(-1).unsqueeze(1)
         else:
-            ls, off = self.model.lengthscale, self.model.offset
-            ls, off = (None if ls is None else ls.detach()), (None if off is None else off.detach())
             e = ops.kernel_matrix_per_class(zs, None, self.kernel_type, ls, off)[:, pick]
             ex = ops.kernel_matrix_per_class(zq, zs, self.kernel_type, ls, off)[:, pick]
             exx = torch.diagonal(ops.kernel_matrix_per_class(zq, None, self.kernel_type, ls, off)[:, pick], dim1=-2, dim2=-1)
@@ -781,17 +809,13 @@ class DKT(MetaTemplate):
         stats, count_this, avg_loss = out
         stats = stats.cpu()                                   # the only read-back of the episode
         if stats[1].item() != 0:
-            raise RuntimeError("DKT.correct: kernel matrix not positive definite after jitter retries")
+            _not_pd("DKT.correct")
         return float(stats[0].item()), count_this, avg_loss
 
-    def _adapt_bernoulli(self, x, N):
-        """N Adam steps on the GP hyper-parameters under the Laplace objective of the support set; returns the mean loss."""
-        x_support, _ = self._split(x)
-        y_targets = self._targets(self.n_way, self.n_support, self.device)
-        z_train = self._embed(x_support).detach()
-        self.model.train()
-        self.likelihood.train()
-        self.feature_extractor.eval()
+    def _adapt(self, z_train, y_targets, N):
+        """Test-time adaptation (DKT.py:242-256): N Adam steps (lr 1e-3) on the GP hyper-parameters only, under the model's own objective of the support set;
+        returns the mean loss and leaves the model in eval mode."""
+        self._mode(True, False)
         optimizer = torch.optim.Adam([{'params': self.model.parameters()}], lr=1e-3)
         total = 0.0
         for _ in range(N):
@@ -800,30 +824,46 @@ class DKT(MetaTemplate):
             loss.backward()
             optimizer.step()
             total = total + loss.item()
-        self.model.eval()
-        self.likelihood.eval()
+        self._mode(False)
         return total / float(N + 1e-10)
+
+    def _episode_posterior(self, x, N=0):
+        """The posterior of a test episode x [n_way, n_support + n_query, ...]: (mu [C,M], labels [M], out, avg_loss).  The fused eval front end where it
+        applies (N = 0: one backbone pass over support and queries); otherwise embed the support set, adapt (N > 0), eval mode, embed the queries, _posterior."""
+        x_support, x_query = self._split(x)
+        y_targets = self._targets(self.n_way, self.n_support, self.device)
+        fused = None
+        if N == 0:
+            with torch.no_grad():
+                fused = self._posterior_fused_eval(x_support, x_query, y_targets)
+        z_train = self._embed(x_support).detach() if fused is None else None
+        avg_loss = self._adapt(z_train, y_targets, N) if N > 0 else 0.0
+        with torch.no_grad():
+            self._mode(False)
+            if fused is None:
+                fused = self._posterior(z_train, y_targets, self._embed(x_query).detach())
+        return fused + (avg_loss,)
 
     def _correct_device(self, x, N=0, laplace=False):
         """`correct` without the read-back: returns (stats, count, avg_loss) with stats = [top1_correct, max |info|] on the device."""
         self._check_way(self.n_way)
         avg_loss = 0.0
         if self.likelihood_type == "bernoulli":
-            # a model trained under the Bernoulli likelihood adapts (N > 0: the GP hyper-parameters only, DKT.py:242-256) and predicts under it
+            # a model trained under the Bernoulli likelihood adapts (N > 0: the GP hyper-parameters only) and predicts under it
             laplace = laplace or "deep"
             if N > 0:
-                avg_loss = self._adapt_bernoulli(x, N)
+                avg_loss = self._adapt(self._embed(self._split(x)[0]).detach(), self._targets(self.n_way, self.n_support, self.device), N)
         if laplace and (laplace == "deep" or ops.laplace_supported(self.n_way * self.n_support, self.n_way)):
             # Laplace GPC on the device: 1.0 * RBF(0.1) as the reference fits it, or the model's own kernel; top1 counted on the device
             labels = self._laplace_device(x, "deep" if laplace == "deep" else "rbf0.1")[3][0]
             y_q = torch.arange(self.n_way, device=labels.device, dtype=torch.int32).repeat_interleave(self.n_query)
             return torch.stack([(labels == y_q).sum().float(), torch.zeros((), device=labels.device)]), self.n_way * self.n_query, avg_loss
-        x_support, x_query = self._split(x)
-        y_query = np.repeat(range(self.n_way), self.n_query)
 
         if laplace:   # more than 127 support rows: sklearn Laplace GPC, "not the method used in the paper" (DKT.py:207-222)
             from sklearn.gaussian_process import GaussianProcessClassifier
             from sklearn.gaussian_process.kernels import RBF
+            x_support, x_query = self._split(x)
+            y_query = np.repeat(range(self.n_way), self.n_query)
             y_support = np.repeat(range(self.n_way), self.n_support)
             kernel = 1.0 * RBF(length_scale=0.1, length_scale_bounds=(0.1, 10.0))
             gp = GaussianProcessClassifier(kernel=kernel, optimizer=None)
@@ -834,45 +874,22 @@ class DKT(MetaTemplate):
             y_pred = gp.predict(z_query.cpu().numpy())
             return float(np.sum(y_pred == y_query)), len(y_query), 0.0
 
-        dev = self.device
-        y_targets = self._targets(self.n_way, self.n_support, dev)
-        fused = None
-        if N == 0:
-            with torch.no_grad():
-                fused = self._posterior_fused_eval(x_support, x_query, y_targets)
-        z_train = self._embed(x_support).detach() if fused is None else None
-
-        self.model.train()
-        self.likelihood.train()
-        self.feature_extractor.eval()
-
-        avg_loss = 0.0
-        if N > 0:   # test-time adaptation of the GP hyper-parameters only (DKT.py:242-256)
-            optimizer = torch.optim.Adam([{'params': self.model.parameters()}], lr=1e-3)
-            for _ in range(0, N):
-                optimizer.zero_grad()
-                loss, _ = self._episode_loss(z_train, y_targets)
-                loss.backward()
-                optimizer.step()
-                avg_loss = avg_loss + loss.item()
-
+        _, labels, out, avg_loss = self._episode_posterior(x, N)
         with torch.no_grad():
-            self.model.eval()
-            self.likelihood.eval()
-            self.feature_extractor.eval()
-            if fused is None:
-                z_query = self._embed(x_query).detach()
-                _, labels, out = self._posterior(z_train, y_targets, z_query)
-            else:
-                _, labels, out = fused
-            y_q = torch.arange(self.n_way, device=dev, dtype=torch.int32).repeat_interleave(self.n_query)
+            y_q = torch.arange(self.n_way, device=self.device, dtype=torch.int32).repeat_interleave(self.n_query)
             stats = torch.stack([(labels == y_q).sum().float(), out["info"].abs().max().float()])
-            count_this = len(y_query)
-        return stats, count_this, avg_loss / float(N + 1e-10)
+        return stats, self.n_way * self.n_query, avg_loss
 
     def test_loop(self, test_loader, record=None, return_std=False):
         acc_all, pending = [], []
         iter_num = len(test_loader)
+
+        def flush():          # ONE read-back of the pending per-episode (stats, count)
+            got = torch.stack([p[0] for p in pending]).cpu().numpy()
+            if (got[:, 1] != 0).any():
+                _not_pd("DKT.test_loop")
+            acc_all.extend((got[:, 0] / np.asarray([p[1] for p in pending]) * 100).tolist())
+            del pending[:]
         for i, (x, _) in enumerate(test_loader):
             self.n_query = x.size(1) - self.n_support
             if self.change_way:
@@ -883,19 +900,12 @@ class DKT(MetaTemplate):
                 stats = torch.tensor([stats, 0.0], device=self.device)
             pending.append((stats, count_this))
             if i % 100 == 0 or i == iter_num - 1:
-                got = torch.stack([p[0] for p in pending]).cpu().numpy()
-                if (got[:, 1] != 0).any():
-                    raise RuntimeError("DKT.test_loop: kernel matrix not positive definite after jitter retries")
-                acc_all.extend((got[:, 0] / np.asarray([p[1] for p in pending]) * 100).tolist())
-                pending = []
+                flush()
             if i % 100 == 0:
                 acc_mean = np.mean(np.asarray(acc_all))
                 print('Test | Batch {:d}/{:d} | Loss {:f} | Acc {:f}'.format(i, len(test_loader), loss_value, acc_mean))
         if pending:                                            # a loader whose length is unknown / shorter than announced
-            got = torch.stack([p[0] for p in pending]).cpu().numpy()
-            if (got[:, 1] != 0).any():
-                raise RuntimeError("DKT.test_loop: kernel matrix not positive definite after jitter retries")
-            acc_all.extend((got[:, 0] / np.asarray([p[1] for p in pending]) * 100).tolist())
+            flush()
         if distributed.is_distributed():   # every rank evaluated its own shard of the episode list
             acc_all = distributed.gather_accuracies(acc_all)
             iter_num = len(acc_all)
@@ -912,18 +922,4 @@ class DKT(MetaTemplate):
     def get_logits(self, x):
         self.n_query = x.size(1) - self.n_support
         self._check_way(self.n_way)
-        x_support, x_query = self._split(x)
-        y_targets = self._targets(self.n_way, self.n_support, self.device)
-        with torch.no_grad():
-            fused = self._posterior_fused_eval(x_support, x_query, y_targets)
-        z_train = self._embed(x_support).detach() if fused is None else None
-        with torch.no_grad():
-            self.model.eval()
-            self.likelihood.eval()
-            self.feature_extractor.eval()
-            if fused is None:
-                z_query = self._embed(x_query).detach()
-                mu, _, _ = self._posterior(z_train, y_targets, z_query)
-            else:
-                mu = fused[0]
-        return mu.t().contiguous()    # [n_way*n_query, n_way] raw posterior means (DKT.py:331-335)
+        return self._episode_posterior(x)[0].t().contiguous()    # [n_way*n_query, n_way] raw posterior means (DKT.py:331-335)

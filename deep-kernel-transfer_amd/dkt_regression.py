@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import configs, ops
-from .dkt import amp_mode, backbone_autocast, gp_head
+from .dkt import amp_property, backbone_autocast, gp_head
 from .gp import ExactGPHypers, RBF_KINDS, SPECTRAL_KINDS
 
 
@@ -56,13 +56,7 @@ class DKT(nn.Module):
     def device(self):
         return self.model.mean_constant.device
 
-    @property
-    def amp(self):
-        return self._amp
-
-    @amp.setter
-    def amp(self, value):
-        object.__setattr__(self, "_amp", amp_mode(value))
+    amp = amp_property
 
     def _features(self, x):
         """Backbone features for the GP: under amp="bf16" (or a caller's torch.autocast) the backbone runs in 16 bits and its output is converted
@@ -70,6 +64,13 @@ class DKT(nn.Module):
         with backbone_autocast(self.amp):
             z = self.feature_extractor(x)
         return z.float()
+
+    def _base_matrix(self, zb):
+        """The differentiable base matrix E [B,N,N] of the tasks zb [B,N,D]."""
+        m = self.model
+        if self.kernel_type in SPECTRAL_KINDS:
+            return ops.spectral_mixture_matrix(zb, m.mixture_weights, m.mixture_means, m.mixture_scales)
+        return ops.base_matrix(zb, self.kernel_type, m.lengthscale)
 
     @gp_head
     def _loss(self, z, labels):
@@ -79,11 +80,7 @@ class DKT(nn.Module):
         n = zb.shape[1]
         m = self.model
         cw = torch.full((1,), -1.0 / n, device=zb.device, dtype=torch.float32)
-        if self.kernel_type in SPECTRAL_KINDS:
-            e = ops.spectral_mixture_matrix(zb, m.mixture_weights, m.mixture_means, m.mixture_scales)
-        else:
-            e = ops.base_matrix(zb, self.kernel_type, m.lengthscale)
-        obj, logp, alpha, info, jit = ops.mll_objective(e, yb, m.scale_times_variance(), m.mean, m.noise, cw,
+        obj, logp, alpha, info, jit = ops.mll_objective(self._base_matrix(zb), yb, m.scale_times_variance(), m.mean, m.noise, cw,
                                                         self.jitter0, self.max_tries)
         return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=jit)
 

@@ -114,17 +114,9 @@ class SinesDKT(DKT):
         m = self.model
         return m.mixture_weights, m.mixture_means, m.mixture_scales
 
-    @gp_head
-    def _loss(self, z, labels):
-        """mean over the B tasks of -logp / N; z [B,N,40] (or [N,40]), labels [B,N] (or [N])."""
-        zb = z if z.dim() == 3 else z.unsqueeze(0)
-        yb = labels.reshape(zb.shape[0], 1, zb.shape[1]).to(torch.float32)
-        n = zb.shape[1]
-        m = self.model
-        cw = torch.full((1,), -1.0 / n, device=zb.device, dtype=torch.float32)
-        e = ops.spectral_mixture_matrix_task(zb, *self._mixture())
-        obj, logp, alpha, info, jit = ops.mll_objective(e, yb, m.scale_times_variance(), m.mean, m.noise, cw, self.jitter0, self.max_tries)
-        return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=jit)
+    def _base_matrix(self, zb):
+        """E [B,N,N] of the tasks zb [B,N,40] on the task-resident kernels."""
+        return ops.spectral_mixture_matrix_task(zb, *self._mixture())
 
     def train_loop(self, step, optimizer, tasks_per_step: int = 1, sampler: SineTaskSampler = None, n_shot: int = 10):
         """One Adam step on the mean over `tasks_per_step` tasks of -logp / N (sines/train_DKT.py:162-180 for B = 1).  Every 100 steps the
