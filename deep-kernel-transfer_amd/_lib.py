@@ -35,7 +35,7 @@ _ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(_ROOT, "include")
 SOURCES = ["dkt_gram.hip", "dkt_gram_ep.hip", "dkt_gram_big.hip", "dkt_gram_small.hip", "dkt_classkernel.hip", "dkt_mll.hip", "dkt_mll_mfma.hip", "dkt_mll_h2.hip", "dkt_mll_reg.hip", "dkt_mll_big.hip", "dkt_mll_tiled.hip", "dkt_mll_band.hip", "dkt_objective.hip", "dkt_predict.hip",
-           "dkt_spectral.hip", "dkt_frontend.hip", "dkt_frontend_big.hip", "dkt_lowrank.hip", "dkt_laplace_grad.hip"]
+           "dkt_spectral.hip", "dkt_frontend.hip", "dkt_frontend_big.hip", "dkt_lowrank.hip", "dkt_mll_rownoise.hip", "dkt_laplace_grad.hip"]
 OBJ_DIR = os.path.join(_HERE, "build")
 
 _c_p = ctypes.c_void_p
@@ -82,8 +82,13 @@ SIGNATURES = {
     "dkt_smk_bwd_f32": (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p]),
     "dkt_laplace_grad_workspace_bytes": (ctypes.c_size_t, [_c_i, _c_i, _c_i]),
     "dkt_laplace_grad_f32": (_c_i, [_c_p, ctypes.c_long, ctypes.c_long, _c_p, _c_p, ctypes.c_long] + [_c_p] * 5 + [_c_i, _c_i, _c_i, _c_p, ctypes.c_size_t, _c_p]),
+    "dkt_mll_rownoise_workspace_bytes": (ctypes.c_size_t, [_c_i, _c_i, _c_i]),
+    "dkt_mll_rownoise_f32": (_c_i, [_c_p, ctypes.c_long, ctypes.c_long, _c_p, ctypes.c_long, _c_p, ctypes.c_long] + [_c_p] * 10 + [_c_i, _c_i, _c_i, ctypes.c_uint,
+                                    _c_p, ctypes.c_size_t, _c_p]),
+    "dkt_dirichlet_proba_f32": (_c_i, [_c_p] * 5 + [_c_i, _c_i, _c_i, _c_i, _c_p]),
 }
-LAPLACE_MAX_N, LAPLACE_MAX_C = 127, 32      # DKT_LAPLACE_MAX_N / _C of include/dkt_abi.h (DKT_ERR_SHAPE outside them): the limits of dkt_gpc_mode_f32
+LAPLACE_MAX_N, LAPLACE_MAX_C = 127, 32      # DKT_LAPLACE_MAX_N / _C of include/dkt_abi.h (DKT_ERR_SHAPE outside them): the limits of dkt_gpc_mode_f32,
+                                            # and of dkt_mll_rownoise_f32 / dkt_dirichlet_proba_f32
 
 # libdkt_x16.so (include/dkt_abi_x16.h; tests check that this lists every function of the header): each front-end call of SIGNATURES with `int xdtype` after X
 X_BF16 = 1

@@ -10,6 +10,10 @@ kernel_type = 'bncossim'
 # The drivers' `--amp` flag sets it (io_utils.parse_args), as `--kernel_type` feeds kernel_type.
 amp = None
 
+# likelihood of the DKT models a process builds when their constructor is not told (likelihood=None): None (= 'gaussian'), 'bernoulli' or 'dirichlet'.
+# `--likelihood` of the evaluation drivers sets it (io_utils.parse_args('test')), for the same reason as amp: test_uncertainty.py does not pass the flag on.
+likelihood = None
+
 save_dir = './save/'                     # checkpoints: <save_dir>checkpoints/<dataset>/<model>_<method>[_aug]_<n>way_<k>shot
 
 # file-list roots of the image datasets (image_data.FilelistEpisodeLoader; `--dataset synthetic` needs none)

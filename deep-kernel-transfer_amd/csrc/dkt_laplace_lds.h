@@ -38,19 +38,31 @@ __device__ __forceinline__ void build_b_lower(float* sA, const float* sK, const 
 
 // right-looking Cholesky: column j scaled by its pivot (kept apart in sd: the pivot entry itself is only read here), then the trailing update; two
 // barriers per column.  L is the strict lower triangle of sA with sd as its diagonal; the upper triangle is not touched.
-template <int T>
-__device__ __forceinline__ void cholesky_lower(float* sA, float* sd, int N, int NP, int tid) {
+// ROWS >= N rows take part: a row i >= N (a right-hand side carried along, dkt_mll_rownoise.hip) has no diagonal entry and comes out as L^-1 times it.
+// CHECK: a pivot that is not finite and positive ends the sweep; returns 1 + its index, else 0 (every thread reads the same pivot, so the whole
+// workgroup leaves together).
+template <int T, bool CHECK>
+__device__ __forceinline__ int cholesky_lower_rows(float* sA, float* sd, int N, int rows, int NP, int tid) {
     for (int j = 0; j < N; ++j) {
-        float d = sqrtf(sA[j * NP + j]);
-        for (int i = j + 1 + tid; i < N; i += T) sA[i * NP + j] = sA[i * NP + j] / d;
+        const float p = sA[j * NP + j];
+        if (CHECK && !(p > 0.f && p < INFINITY)) return j + 1;
+        float d = sqrtf(p);
+        for (int i = j + 1 + tid; i < rows; i += T) sA[i * NP + j] = sA[i * NP + j] / d;
         if (tid == 0) sd[j] = d;
         __syncthreads();
-        for (int i = j + 1 + tid / 16; i < N; i += T / 16) {
+        for (int i = j + 1 + tid / 16; i < rows; i += T / 16) {
             float lij = sA[i * NP + j];
-            for (int k = j + 1 + (tid & 15); k <= i; k += 16) sA[i * NP + k] -= lij * sA[k * NP + j];
+            const int kend = i < N ? i : N - 1;
+            for (int k = j + 1 + (tid & 15); k <= kend; k += 16) sA[i * NP + k] -= lij * sA[k * NP + j];
         }
         __syncthreads();
     }
+    return 0;
+}
+
+template <int T>
+__device__ __forceinline__ void cholesky_lower(float* sA, float* sd, int N, int NP, int tid) {
+    cholesky_lower_rows<T, false>(sA, sd, N, N, NP, tid);
 }
 
 // row i of lml = -1/2 a.f - sum log(1 + exp(-(2y - 1) f)) - sum log L_ii    (log(1 + exp(-z)) = max(-z, 0) + log1p(exp(-|z|)): no overflow for large |f|)

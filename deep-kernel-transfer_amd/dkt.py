@@ -10,6 +10,8 @@
         laplace="deep": the same with the model's own trained kernel; .laplace_proba(x, kernel) their class probabilities; .laplace the default of test_loop
     .get_logits(x) -> [n_way*n_query, n_way]                 test_uncertainty.py:197
     .set_forward / .set_forward_loss         stubs (DKT.py:73-77)
+    .dirichlet_proba(x, samples, seed) -> class probabilities of a model under likelihood="dirichlet" (docs/DIRICHLET.md), whose .correct / .test_loop /
+        .get_logits condition on the transformed labels of the support set
     .feature / .feature_extractor / .model / .likelihood / .mll / .normalize / .iteration / .writer
 
 What changed underneath: the n_way GPyTorch ExactGP models + SumMarginalLogLikelihood are replaced by
@@ -161,7 +163,7 @@ class _MetaBatched:
                 xs, ys = [], []
 
 
-LIKELIHOODS = ("gaussian", "bernoulli")
+LIKELIHOODS = ("gaussian", "bernoulli", "dirichlet")
 
 
 class _GraphedTrainStep:
@@ -209,12 +211,15 @@ class _GraphedTrainStep:
 
 
 class DKT(MetaTemplate):
-    def __init__(self, model_func, n_way, n_support, kernel_type=None, amp=None, likelihood="gaussian"):
+    def __init__(self, model_func, n_way, n_support, kernel_type=None, amp=None, likelihood=None):
         super(DKT, self).__init__(model_func, n_way, n_support)
+        if likelihood is None:                                # configs.likelihood: the evaluation drivers' --likelihood (None: "gaussian")
+            likelihood = configs.likelihood or "gaussian"
         if likelihood not in LIKELIHOODS:
             raise ValueError("likelihood must be one of %s, got %r" % (LIKELIHOODS, likelihood))
         # "gaussian": regression on +-1 labels (the paper's method, the reference's only objective); "bernoulli": the Laplace approximation of the log marginal
-        # likelihood under a Bernoulli likelihood (docs/LAPLACE.md "Training"; up to 127 rows per episode).  Not a module, parameter or buffer: the state dict is the same
+        # likelihood under a Bernoulli likelihood (docs/LAPLACE.md "Training"; up to 127 rows per episode); "dirichlet": the exact marginal likelihood of the class
+        # labels as Gaussian targets with a fixed noise per row (docs/DIRICHLET.md; up to 127 rows).  Not a module, parameter or buffer: the state dict is the same
         self.likelihood_type = likelihood
         self.kernel_type = configs.kernel_type if kernel_type is None else kernel_type
         # mixed-precision backbone (opt-in): "bf16" runs the backbone under torch.autocast up to, not including, bn_out; the GP head stays fp32.
@@ -301,12 +306,32 @@ class DKT(MetaTemplate):
         return y
 
     @staticmethod
-    def _check_bernoulli_rows(n, c=1):
+    def _check_resident_rows(n, c=1, likelihood="bernoulli", rows="n_way * (n_support + n_query)"):
+        """The limits of the LDS-resident kernels behind the Bernoulli and the Dirichlet likelihood: 127 rows, 32 classes."""
         if c > ops._lib.LAPLACE_MAX_C:
-            raise ValueError("likelihood='bernoulli' takes up to %d classes, the episode has %d" % (ops._lib.LAPLACE_MAX_C, c))
+            raise ValueError("likelihood='%s' takes up to %d classes, the episode has %d" % (likelihood, ops._lib.LAPLACE_MAX_C, c))
         if n > ops._lib.LAPLACE_MAX_N:
-            raise ValueError("likelihood='bernoulli' takes episodes of up to %d rows (n_way * (n_support + n_query)), this one has %d"
-                             % (ops._lib.LAPLACE_MAX_N, n))
+            raise ValueError("likelihood='%s' takes episodes of up to %d rows (%s), this one has %d" % (likelihood, ops._lib.LAPLACE_MAX_N, rows, n))
+
+    def _dirichlet_targets(self, y):
+        """(ytilde, noise_rows) of the +-1 one-vs-rest targets y (ops.dirichlet_targets), built once per target tensor of `_targets`."""
+        key = ("dirichlet", y.data_ptr(), tuple(y.shape), str(y.device))
+        t = self._target_cache.get(key)
+        if t is None:
+            t = ops.dirichlet_targets(y) + (y,)           # (y is kept: its address is the key)
+            self._target_cache[key] = t
+        return t[0], t[1]
+
+    def _condition(self, e, y, sv, mean, noise):
+        """The mean cache (alpha) of the class models on a conditioning set with base matrix e and +-1 targets y, under the model's likelihood: the Gaussian
+        posterior of ops.mll, or -- likelihood="dirichlet" -- that of the transformed labels with their noise per row (ops.mll_rownoise; no jitter ladder)."""
+        if self.likelihood_type != "dirichlet":
+            return ops.mll(e, y, sv, mean, noise, jitter0=self.jitter0, max_tries=self.max_tries)
+        self._check_resident_rows(e.shape[-1], y.shape[-2], "dirichlet", "the conditioning set")
+        yt, nr = self._dirichlet_targets(y)
+        out = ops.mll_rownoise(e, yt, nr, sv, mean)
+        out["jitter"] = torch.zeros_like(out["logp"])
+        return out
 
     @staticmethod
     def _bernoulli_targets(y):
@@ -391,11 +416,18 @@ class DKT(MetaTemplate):
         cw = torch.full((c,), -1.0 / (c * n), device=xb.device, dtype=torch.float32)
         bn = self._bn_out(True)
         if self.likelihood_type == "bernoulli":
-            self._check_bernoulli_rows(n, c)
+            self._check_resident_rows(n, c)
             obj, logp, iters, e, bmean, bvar, a, s, rnorm = ops.episode_loss_laplace_bn(
                 xb, None if bn is None else bn.weight, None if bn is None else bn.bias, self._bernoulli_targets(y), sv, cw,
                 eps=1e-5 if bn is None else bn.eps, use_bn=bn is not None)
             alpha, jit, info = None, None, torch.zeros_like(iters)      # (B = I + W^1/2 K W^1/2 has eigenvalues >= 1: no jitter ladder, nothing can fail)
+        elif self.likelihood_type == "dirichlet":
+            self._check_resident_rows(n, c, "dirichlet")
+            yt, nr = self._dirichlet_targets(y)
+            obj, logp, alpha, info, e, bmean, bvar, a, s, rnorm = ops.episode_loss_dirichlet_bn(
+                xb, None if bn is None else bn.weight, None if bn is None else bn.bias, yt, nr, sv, mean, cw,
+                eps=1e-5 if bn is None else bn.eps, use_bn=bn is not None)
+            jit = None
         else:
             if bn is not None:
                 outs = ops.episode_loss_bn(xb, bn.weight, bn.bias, y, sv, mean, noise, cw, eps=bn.eps, jitter0=self.jitter0,
@@ -446,11 +478,19 @@ class DKT(MetaTemplate):
         if self.likelihood_type == "bernoulli":
             # minimise -(1/C) sum_c lml_c / N of the Laplace approximation (the reference's SumMarginalLogLikelihood / ExactMarginalLogLikelihood scaling,
             # DKT.py:160-163); the Gaussian noise and the constant mean do not enter this model and receive no gradient
-            self._check_bernoulli_rows(n, c)
+            self._check_resident_rows(n, c)
             obj, logp, iters, e = ops.episode_loss_laplace(zb, self._bernoulli_targets(y), sv, cw, self.kernel_type, self.model.lengthscale, self.model.offset,
                                                            unit_rows=bool(self.normalize))
             aux = dict(logp=logp, alpha=None, info=torch.zeros_like(iters), jitter=None, e=e.detach(), iters=iters)
             return obj.mean(), aux
+        if self.likelihood_type == "dirichlet":
+            # minimise -(1/C) sum_c logp_c / N of the C = n_way exact GPs on the transformed labels (the same scaling); outputscale and the constant mean train, the
+            # noise is the likelihood's own per row and the frozen Gaussian noise does not enter
+            self._check_resident_rows(n, c, "dirichlet")
+            yt, nr = self._dirichlet_targets(y)
+            obj, logp, alpha, info, e = ops.episode_loss_dirichlet(zb, yt, nr, sv, mean, cw, self.kernel_type, self.model.lengthscale, self.model.offset,
+                                                                   unit_rows=bool(self.normalize))
+            return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=None, e=e.detach())
         if self.kernel_type in LINEAR_KINDS:
             obj, logp, alpha, info, jit, e = ops.episode_loss_linear(zb, y, sv, mean, noise, cw, self.jitter0, self.max_tries,
                                                                      unit_rows=bool(self.normalize))
@@ -487,7 +527,7 @@ class DKT(MetaTemplate):
         if self.kernel_type in LINEAR_KINDS:
             if e_cond is None:
                 e_cond = ops.kernel_matrix(zc, None, self.kernel_type)
-            out = ops.mll(e_cond, y, sv, mean, noise, jitter0=self.jitter0, max_tries=self.max_tries)
+            out = self._condition(e_cond, y, sv, mean, noise)
             mu, labels = ops.predict(ops.kernel_matrix(zs, zc, self.kernel_type), out["alpha"], sv, mean)
             return mu[0], labels[0], out
         # per-class base matrices (E depends on the class model's own, post-step, lengthscale / offset)
@@ -498,7 +538,7 @@ class DKT(MetaTemplate):
         mus, outs = [], []
         for s in groups:
             yk, svk, meank, noisek, lsk, offk = _class_cut(s, y, sv, mean, noise, ls, off)
-            o = ops.mll(kmat(zc, None, self.kernel_type, lsk, offk), yk, svk, meank, noisek, jitter0=self.jitter0, max_tries=self.max_tries)
+            o = self._condition(kmat(zc, None, self.kernel_type, lsk, offk), yk, svk, meank, noisek)
             m, labels = ops.predict(kmat(zs, zc, self.kernel_type, lsk, offk), o["alpha"], svk, meank, want_labels=len(groups) == 1)
             mus.append(m); outs.append(o)
         if len(groups) == 1:                                 # (the labels come from the predict kernel)
@@ -539,7 +579,7 @@ class DKT(MetaTemplate):
             zn, _ = ops.affine_normalize(x_feat.unsqueeze(0).contiguous(), a.contiguous(), s.contiguous())
             e_all = ops.gram(zn, None, ops.KERNEL_LINEAR_UNIT)
         sv, mean, noise, _, _ = self._hypers_detached()
-        out = ops.mll(e_all[:, :ns, :ns].contiguous(), y, sv, mean, noise, jitter0=self.jitter0, max_tries=self.max_tries)
+        out = self._condition(e_all[:, :ns, :ns].contiguous(), y, sv, mean, noise)
         mu, labels = ops.predict(e_all[:, ns:, :ns].contiguous(), out["alpha"], sv, mean)
         return mu[0], labels[0], out
 
@@ -801,6 +841,44 @@ class DKT(MetaTemplate):
         prob = self._laplace_device(x, kernel, batched)[2].transpose(1, 2)
         prob = torch.cat([1.0 - prob, prob], 2) if self.n_way == 2 else prob / prob.sum(2, keepdim=True)
         return prob.contiguous() if batched else prob[0].contiguous()
+
+    # ---- Dirichlet classification likelihood: class probabilities of the latent posterior (docs/DIRICHLET.md) ----
+    def _dirichlet_device(self, x, batched=False):
+        """An episode x [n_way, n_support + n_query, ...] (batched: B of them) -> the latent posterior of the queries under the Dirichlet likelihood, conditioned
+        on the support set with the model's own kernel: (mu, var [B,C,M]).  One backbone pass per episode, as in `_laplace_device`."""
+        self._check_way(self.n_way)
+        xd = self._upload(x if batched else x.unsqueeze(0))
+        ns, nq = self.n_way * self.n_support, self.n_way * (xd.shape[2] - self.n_support)
+        self._check_resident_rows(ns, self.n_way, "dirichlet", "n_way * n_support")
+        with torch.no_grad():
+            self._mode(False)
+            z = torch.stack([self._embed(torch.cat([xe[:, :self.n_support].reshape(ns, *xe.shape[2:]), xe[:, self.n_support:].reshape(nq, *xe.shape[2:])], 0))
+                             for xe in xd], 0).detach().float()
+            zs, zq = z[:, :ns].contiguous(), z[:, ns:].contiguous()
+            sv, mean, _, ls, off = self._hypers_detached()
+            yt, nr = self._dirichlet_targets(self._targets(self.n_way, self.n_support, z.device))
+            zero = torch.zeros_like(sv)                       # the LATENT variance: no observation noise on the queries
+            if self.kernel_type in LINEAR_KINDS:
+                ex = ops.kernel_matrix(zq, zs, self.kernel_type)
+                out = ops.mll_rownoise(ops.kernel_matrix(zs, None, self.kernel_type), yt, nr, sv, mean, want_chol=True)
+                return ops.predict(ex, out["alpha"], sv, mean, want_labels=False)[0], ops.predict_var(ex, (zq * zq).sum(-1), out["chol"], sv, zero)
+            ex = ops.kernel_matrix_per_class(zq, zs, self.kernel_type, ls, off)
+            exx = torch.diagonal(ops.kernel_matrix_per_class(zq, None, self.kernel_type, ls, off), dim1=-2, dim2=-1)
+            out = ops.mll_rownoise(ops.kernel_matrix_per_class(zs, None, self.kernel_type, ls, off), yt, nr, sv, mean, want_chol=True)
+            mu = ops.predict(ex, out["alpha"], sv, mean, want_labels=False)[0]
+            # (dkt_predict_var_f32 takes one cross kernel for the class models it is given: a call per class model here)
+            var = torch.cat([ops.predict_var(ex[:, k].contiguous(), exx[:, k].contiguous(), out["chol"][:, k:k + 1].contiguous(), sv[k:k + 1], zero[k:k + 1])
+                             for k in range(self.n_way)], 1)
+            return mu, var
+
+    def dirichlet_proba(self, x, samples=256, seed=0, batched=False):
+        """Class probabilities under the Dirichlet likelihood, [n_way * n_query, n_way] (batched: x is [B, n_way, ...] and the result [B, n_way * n_query, n_way]):
+        the mean over `samples` draws of the softmax of the latent posterior, rows summing to 1 (Milios et al. 2018, eq. 8).  The standard normals come from a
+        generator seeded with `seed` and are shared by every query and episode (ops.dirichlet_proba), so the result is a deterministic function of x."""
+        mu, var = self._dirichlet_device(x, batched)
+        eps = torch.randn(int(samples), self.n_way, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float32).to(mu.device)
+        prob = ops.dirichlet_proba(mu, var, eps)[0]
+        return prob if batched else prob[0]
 
     def correct(self, x, N=0, laplace=False):
         out = self._correct_device(x, N, laplace)

@@ -41,8 +41,8 @@ def parse_args(script, argv=None):
     parser.add_argument('--image_size', default=None, type=int, help='override the backbone-dependent image size')
     parser.add_argument('--n_episode', default=None, type=int, help='episodes per epoch (train: 100) / per test run (600)')
     parser.add_argument('--meta_batch', default=1, type=int, help='[train, this build] episodes per Adam step through the batched hot path (1 = the reference: one step per episode)')
-    parser.add_argument('--likelihood', default='gaussian', choices=['gaussian', 'bernoulli'],
-                        help='[this build] gaussian: regression on +-1 labels (the reference); bernoulli: the Laplace marginal likelihood of a GP classifier, episodes of up to 127 rows (default: gaussian)')
+    parser.add_argument('--likelihood', default='gaussian', choices=['gaussian', 'bernoulli', 'dirichlet'],
+                        help='[this build] gaussian: regression on +-1 labels (the reference); bernoulli: the Laplace marginal likelihood of a GP classifier, episodes of up to 127 rows; dirichlet: the exact marginal likelihood of the labels as Gaussian targets with a noise per row (Milios et al. 2018), up to 127 rows (default: gaussian)')
     _add_amp(parser)
     if script == 'train':
         parser.add_argument('--num_classes', default=200, type=int, help='(baseline only; kept for CLI compatibility)')
@@ -58,7 +58,12 @@ def parse_args(script, argv=None):
         parser.add_argument('--repeat', default=5, type=int, help='Repeat the test N times with different seeds')
     else:
         raise ValueError('Unknown script')
-    return _apply_amp(parser.parse_args(argv))
+    args = _apply_amp(parser.parse_args(argv))
+    if script == 'test':
+        # the default of every DKT the process builds, as --amp is: test_uncertainty.py constructs its model without passing the flag on, and would otherwise
+        # evaluate a checkpoint trained under one likelihood with the posterior of another
+        configs.likelihood = args.likelihood
+    return args
 
 
 def parse_args_regression(script, argv=None):
@@ -81,7 +86,12 @@ def parse_args_regression(script, argv=None):
         parser.add_argument('--n_test_epochs', default=10, type=int, help='How many test people?')
     else:
         raise ValueError('Unknown script')
-    return _apply_amp(parser.parse_args(argv))
+    args = _apply_amp(parser.parse_args(argv))
+    if script == 'test':
+        # the default of every DKT the process builds, as --amp is: test_uncertainty.py constructs its model without passing the flag on, and would otherwise
+        # evaluate a checkpoint trained under one likelihood with the posterior of another
+        configs.likelihood = args.likelihood
+    return args
 
 
 def parse_args_sines(argv=None):
@@ -130,6 +140,8 @@ def checkpoint_dir_for(params, save_dir):
     d += '_%dway_%dshot' % (params.train_n_way, params.n_shot)
     if getattr(params, 'likelihood', 'gaussian') == 'bernoulli':         # (the Gaussian default keeps the reference's directory name)
         d += '_bernoulli'
+    elif getattr(params, 'likelihood', 'gaussian') == 'dirichlet':
+        d += '_dirichlet'
     return d
 
 

@@ -9,6 +9,8 @@ Autograd surface
   episode_loss_linear(z, y, sv, mean, noise, cls_weight) -> obj[B]   (fused: gram -> mll -> gram_bwd)
   base_matrix(z, kind, lengthscale) -> E[B,N,N]                       (differentiable Gram / RBF)
   mll_objective(e, y, sv, mean, noise, cls_weight) -> obj[B], aux     (differentiable in e, sv, mean, noise)
+  laplace_objective / dirichlet_objective and their episode_loss_* forms: the same episode under a Bernoulli (Laplace approximation) or a
+  Dirichlet classification likelihood (docs/LAPLACE.md, docs/DIRICHLET.md)
 which replace `-self.mll(self.model(*inputs), targets)` + `.backward()` of the reference
 (methods/DKT.py:161-163, methods/DKT_regression.py:53-56).
 """
@@ -709,6 +711,78 @@ def _laplace_forward(K, Y, cls_weight, scale, max_iter):
         return objective(lml, cls_weight), lml, md["iters"], dk, dscale
 
 
+# Dirichlet classification likelihood (Milios et al. 2018; docs/DIRICHLET.md): class labels as Gaussian targets with a fixed noise per row, exact inference
+def dirichlet_targets(y_pm1: torch.Tensor, alpha_eps: float = 0.01):
+    """+-1 one-vs-rest labels -> (ytilde, noise_rows) of the same shape: a = alpha_eps + [y > 0], noise_rows = log(1 / a + 1), ytilde = log a - noise_rows / 2
+    (the log-normal match of the Gamma marginals of a Dirichlet: 0.688184, -0.334142 on the positive class and 4.615121, -6.912731 elsewhere at 0.01)."""
+    a = float(alpha_eps) + (y_pm1 > 0).to(torch.float32)
+    noise_rows = torch.log(1.0 / a + 1.0)
+    return (torch.log(a) - 0.5 * noise_rows).contiguous(), noise_rows.contiguous()
+
+
+def mll_rownoise(e: torch.Tensor, y: torch.Tensor, noise_rows: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor, want_grad: bool = False,
+                 want_chol: bool = False, cls_weight: Optional[torch.Tensor] = None) -> dict:
+    """Exact-GP marginal log likelihood with a noise per ROW, K_c = sv_c E + diag(noise_rows_c) (dkt_mll_rownoise_f32; N <= 127, C <= 32, no jitter ladder).
+    e: [B,N,N] (shared by the class models) or [B,C,N,N]; y, noise_rows: [C,N] (every episode) or [B,C,N]; sv, mean: C elements.
+    Returns dict(logp [B,C] unweighted, alpha [B,C,N], info [B,C] int32, chol [B,C,N,N] | None, and with want_grad de = cls_weight_c sv_c G_c ([B,C,N,N], or
+    [B,N,N] summed over the classes for a shared e), dsv = cls_weight_c <G_c, e>, dmean = cls_weight_c sum alpha [B,C]), G = d logp / d K."""
+    per_class = e.dim() == 4
+    e = _req(e, "e", 4 if per_class else 3)
+    b_, n = e.shape[0], e.shape[-1]
+    y = _req(y, "y", y.dim() if y.dim() in (2, 3) else 2)
+    noise_rows = _req(noise_rows, "noise_rows", noise_rows.dim() if noise_rows.dim() in (2, 3) else 2)
+    c_ = y.shape[-2]
+    if (e.shape[-2] != n or y.shape[-1] != n or tuple(noise_rows.shape[-2:]) != (c_, n) or (per_class and e.shape[1] != c_)
+            or (y.dim() == 3 and y.shape[0] != b_) or (noise_rows.dim() == 3 and noise_rows.shape[0] != b_)):
+        raise RuntimeError("mll_rownoise: e must be [B,N,N] or [B,C,N,N] and y, noise_rows [C,N] or [B,C,N], got %s, %s and %s"
+                           % (tuple(e.shape), tuple(y.shape), tuple(noise_rows.shape)))
+    sv = _req(sv.reshape(-1), "sv", 1)
+    mean = _req(mean.reshape(-1), "mean", 1)
+    cw = None if cls_weight is None else _req(cls_weight.reshape(-1), "cls_weight", 1)
+    if not (sv.numel() == mean.numel() == c_) or (cw is not None and cw.numel() != c_):
+        raise RuntimeError("mll_rownoise: sv / mean / cls_weight must have C=%d elements" % c_)
+    dev = e.device
+    logp = torch.empty((b_, c_), device=dev, dtype=torch.float32)
+    alpha = torch.empty((b_, c_, n), device=dev, dtype=torch.float32)
+    info = torch.empty((b_, c_), device=dev, dtype=torch.int32)
+    flags = (MLL_WANT_GRAD if want_grad else 0) | (MLL_WANT_CHOL if want_chol else 0)
+    chol = torch.empty((b_, c_, n, n), device=dev, dtype=torch.float32) if want_chol else None
+    de = dsv = dmean = ws = None
+    ws_bytes = 0
+    lib = _lib_now()
+    if want_grad:
+        de = torch.empty((b_, c_, n, n) if per_class else (b_, n, n), device=dev, dtype=torch.float32)
+        dsv = torch.empty((b_, c_), device=dev, dtype=torch.float32)
+        dmean = torch.empty((b_, c_), device=dev, dtype=torch.float32)
+        if not per_class:
+            ws_bytes = int(lib.dkt_mll_rownoise_workspace_bytes(b_, c_, n))
+            ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32) if ws_bytes else None
+    with _timed("dkt_mll_rownoise_f32"):
+        st = lib.dkt_mll_rownoise_f32(_p(e), (c_ if per_class else 1) * n * n, n * n if per_class else 0, _p(y), c_ * n if y.dim() == 3 else 0,
+                                      _p(noise_rows), c_ * n if noise_rows.dim() == 3 else 0, _p(sv), _p(mean), _p(cw), _p(logp), _p(alpha), _p(de),
+                                      _p(dsv), _p(dmean), _p(chol), _p(info), b_, c_, n, flags, _p(ws), ws_bytes, _stream())
+    _lib.check(st, "dkt_mll_rownoise_f32")
+    return dict(logp=logp, alpha=alpha, info=info, chol=chol, de=de, dsv=dsv, dmean=dmean)
+
+
+def dirichlet_proba(mu: torch.Tensor, var: torch.Tensor, eps: torch.Tensor):
+    """prob[b,q,c] = mean_s softmax_c(mu[b,c,q] + sqrt(max(var[b,c,q], 0)) eps[s,c]) (dkt_dirichlet_proba_f32): mu, var [B,C,M] the latent posterior of
+    `predict` / `predict_var` (zero noise), eps [S,C] the caller's standard normals, shared by every query (common random numbers).
+    Returns (prob [B,M,C], labels [B,M] int32 = argmax_c mu, the first maximum)."""
+    mu = _req(mu, "mu", 3)
+    var = _req(var, "var", 3)
+    eps = _req(eps, "eps", 2)
+    b_, c_, m = mu.shape
+    if tuple(var.shape) != (b_, c_, m) or eps.shape[1] != c_ or eps.shape[0] < 1:
+        raise RuntimeError("dirichlet_proba: var must be %s like mu and eps [S,C=%d], got %s and %s" % (tuple(mu.shape), c_, tuple(var.shape), tuple(eps.shape)))
+    prob = torch.empty((b_, m, c_), device=mu.device, dtype=torch.float32)
+    labels = torch.empty((b_, m), device=mu.device, dtype=torch.int32)
+    with _timed("dkt_dirichlet_proba_f32"):
+        st = _lib_now().dkt_dirichlet_proba_f32(_p(mu), _p(var), _p(eps), _p(prob), _p(labels), b_, c_, m, eps.shape[0], _stream())
+    _lib.check(st, "dkt_dirichlet_proba_f32")
+    return prob, labels
+
+
 def _classmap_of(kernel: str, lengthscale, offset):
     """(map id, power, parameter [C], base-matrix kind) of a kernel whose class models own their base-kernel parameter."""
     if kernel in POLY_KINDS:
@@ -1087,7 +1161,7 @@ def normalize_bn_bwd(dzn, zn, x, a, rnorm, mean=None, rstd=None):
 #       exists); saved: the tensors its backward needs; static: shapes and flags for it
 #   objv.forward(m, *objective arguments)  -> (obj [B], aux, saved, static)
 #       aux: its non-differentiable outputs in the order the public functions return them; saved / static as above
-#   objv.de(saved) -> d obj / d E as the forward left it (W of dkt_mll_f32, dK of dkt_laplace_grad_f32); an `on_features` objective has
+#   objv.de(saved) -> d obj / d E as the forward left it (W of dkt_mll_f32, dK of dkt_laplace_grad_f32, dE of dkt_mll_rownoise_f32); an `on_features` objective has
 #       objv.drows(z, saved, gobj) -> dZ instead
 #   front.backward(saved, static, objv, osaved, gobj, *needs_input_grad of the front arguments) -> their gradients, a tuple
 #   objv.backward(saved, static, gobj, *needs_input_grad of the objective arguments)            -> their gradients, a tuple
@@ -1163,6 +1237,30 @@ class _Laplace:
     def backward(saved, sv_shape, gobj, need_y, need_sv, *_):
         _, dscale = saved
         return None, (_sum_episodes(gobj, dscale, sv_shape) if need_sv else None), None, None
+
+
+class _Dirichlet:
+    """Dirichlet classification likelihood, K_c = sv_c E + diag(noise_rows_c) on the transformed labels: logp, dE and the parts of d sv, d mean in ONE call
+    (dkt_mll_rownoise_f32; exact, no Newton loop, no jitter ladder).  Outputs (logp, alpha, info).  Episodes of up to 127 rows: behind the BN trunk front
+    end it takes the resident form only."""
+    on_features, resident_only = False, True
+
+    @staticmethod
+    def forward(e, ytilde, noise_rows, sv, mean, cls_weight):
+        with torch.no_grad():
+            out = mll_rownoise(e, ytilde, noise_rows, sv, mean, want_grad=True, cls_weight=cls_weight)
+            obj = objective(out["logp"], cls_weight)
+        return obj, (out["logp"], out["alpha"], out["info"]), (out["de"], out["dsv"], out["dmean"]), (sv.shape, mean.shape)
+
+    @staticmethod
+    def de(saved):
+        de, *_ = saved
+        return de
+
+    @staticmethod
+    def backward(saved, shapes, gobj, need_y, need_noise_rows, need_sv, need_mean, *_):
+        _, dsv, dmean = saved                                                     # (both carry cls_weight already)
+        return (None, None, _sum_episodes(gobj, dsv, shapes[0]) if need_sv else None, _sum_episodes(gobj, dmean, shapes[1]) if need_mean else None, None)
 
 
 def _rows_grad(objv, osaved, z, gobj, unit_rows):
@@ -1342,6 +1440,28 @@ def episode_loss_laplace(z, y, sv, cls_weight, kernel: str, lengthscale=None, of
 def episode_loss_laplace_bn(x, gamma, beta, y, sv, cls_weight, eps: float = 1e-5, use_bn: bool = True, max_iter: int = 100):
     """x [B,N,D] trunk output BEFORE bn_out, N <= 127.  Returns (obj [B], lml, iters, E, batch_mean, batch_var_unbiased, a, s, rnorm)."""
     return _EpisodeFn.apply(_BnTrunk, _Laplace, x, gamma, beta, eps, use_bn, y, sv, cls_weight, max_iter)
+
+
+def dirichlet_objective(e, ytilde, noise_rows, sv, mean, cls_weight):
+    """Differentiable (in e, sv, mean) Dirichlet-likelihood objective of B episodes: returns (obj [B], logp [B,C], alpha [B,C,N], info [B,C]); arguments as
+    `mll_rownoise`, ytilde / noise_rows of `dirichlet_targets`.  One launch (two for a shared e), no host read-back."""
+    return _EpisodeFn.apply(_GivenE, _Dirichlet, e, ytilde, noise_rows, sv, mean, cls_weight)
+
+
+def episode_loss_dirichlet(z, ytilde, noise_rows, sv, mean, cls_weight, kernel: str, lengthscale=None, offset=None, unit_rows: bool = False):
+    """Dirichlet-likelihood training episode(s) z [B,N,D] (N <= 127, C <= 32): K_c = sv_c * k_c(z, z) + diag(noise_rows_c).
+    Returns (obj [B], logp [B,C], alpha [B,C,N], info [B,C], E)."""
+    z = _req(z, "z", 3)
+    if kernel in LINEAR_KINDS:
+        return _EpisodeFn.apply(_LinearGram, _Dirichlet, z, unit_rows, ytilde, noise_rows, sv, mean, cls_weight)
+    cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
+    return _EpisodeFn.apply(_ClassKernel, _Dirichlet, z, param, cmap, power, base_kind, ytilde, noise_rows, sv, mean, cls_weight)
+
+
+def episode_loss_dirichlet_bn(x, gamma, beta, ytilde, noise_rows, sv, mean, cls_weight, eps: float = 1e-5, use_bn: bool = True):
+    """x [B,N,D] trunk output BEFORE bn_out (float32, bfloat16 or float16), N <= 127.
+    Returns (obj [B], logp, alpha, info, E, batch_mean, batch_var_unbiased, a, s, rnorm)."""
+    return _EpisodeFn.apply(_BnTrunk, _Dirichlet, x, gamma, beta, eps, use_bn, ytilde, noise_rows, sv, mean, cls_weight)
 
 
 def episode_loss_class_kernel(z, y, sv, mean, noise, cls_weight, kernel: str, lengthscale=None, offset=None,

@@ -416,6 +416,43 @@ int dkt_laplace_grad_f32(const float* K, long k_batch_stride, long k_class_strid
                          const float* f_hat, const float* cls_weight, float* lml, float* dK, float* dscale, int B, int C, int N,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * ---- a Dirichlet classification likelihood: the exact-GP marginal likelihood with a noise per ROW, and class probabilities ------------
+ * (additive entries of ABI 7; Milios et al., "Dirichlet-based Gaussian Processes for Large-scale Calibrated Classification", NeurIPS 2018 --
+ * GPyTorch's DirichletClassificationLikelihood; docs/DIRICHLET.md)
+ *
+ * dkt_mll_rownoise_f32 -- problem (b, c): K = sv[c] * (E + b e_batch_stride + c e_class_stride) + diag(noise_rows_c), r = y_c - mean[c]
+ * ([N,N] per problem; e_class_stride 0: the C problems of an episode share one E), targets at Y + b y_batch_stride + c N (y_batch_stride 0: every
+ * episode has the same targets [C,N]), sigma^2 per row > 0 at noise_rows + b nr_batch_stride + c N (same striding).  Strides count elements; sv, mean
+ * [C]; cls_weight [C] or NULL (= 1).
+ *     L = chol(K),  alpha = K^-1 r  -> alpha [B,C,N],  logp = -1/2 r.alpha - sum log L_ii - N/2 log 2 pi  -> logp [B,C] (unweighted)
+ *   flags & DKT_MLL_WANT_GRAD : G = 1/2 (alpha alpha^T - K^-1);  per-class E: dE [B,C,N,N], dE[b,c] = cls_weight[c] sv[c] G;  shared E: dE [B,N,N] =
+ *     sum_c cls_weight[c] sv[c] G_c, the classes in index order (needs the workspace: dkt_mll_rownoise_workspace_bytes(B, C, N) bytes; no other
+ *     form of the call needs one);  dsv [B,C] = cls_weight[c] <G, E>,  dmean [B,C] = cls_weight[c] sum_i alpha_i  (either may be NULL):
+ *     d (cls_weight[c] logp) / d sv[c] and / d mean[c].
+ *   flags & DKT_MLL_WANT_CHOL : chol [B,C,N,N] = L, lower triangle, zeros above (what dkt_predict_var_f32 reads).
+ *   Any other flag: DKT_ERR_BAD_ARG.  dE, dsv, dmean, chol are not touched without their flag.
+ *   info [B,C]: 0, or 1 + the index of the first pivot that is not finite and positive; that problem's logp -- and its alpha, chol and its part
+ *   of dE, dsv, dmean -- are NaN then, the other problems are as they would be without it.  There is NO jitter ladder: the noise is the caller's.
+ * Plain fp32, no atomics: two runs give the same bits, and a shared call's dE is bit for bit the in-order class sum of the per-class call's.
+ * Limits (DKT_ERR_SHAPE outside them, before any launch): 1 <= N <= DKT_LAPLACE_MAX_N, 1 <= C <= DKT_LAPLACE_MAX_C.
+ * Replaces, with a DirichletClassificationLikelihood in the place of the GaussianLikelihood of methods/DKT.py:58-71, the loss of
+ * methods/DKT.py:161-163; dkt_mll_f32 takes one noise per class model only.
+ *
+ * dkt_dirichlet_proba_f32 -- prob[b,q,c] = (1/S) sum_s softmax_c(mu[b,c,q] + sqrt(max(var[b,c,q], 0)) eps[s,c]): mu, var [B,C,M] (the latent
+ * means of dkt_predict_f32 / dkt_predict_per_class_f32 and the latent variances of dkt_predict_var_f32 with a zero noise), eps [S,C] the CALLER's
+ * standard normals, shared by every query and episode (common random numbers); the maximum is subtracted before exp, s is summed in index order.
+ * prob [B,M,C]; labels [B,M] (may be NULL) = argmax_c mu, the first maximum wins as in dkt_predict_f32.  1 <= C <= DKT_LAPLACE_MAX_C
+ * (DKT_ERR_SHAPE), S >= 1.  Replaces the sampling of the GPyTorch Dirichlet tutorial (pred_samples.exp() / its sum over the classes, averaged).
+ */
+size_t dkt_mll_rownoise_workspace_bytes(int B, int C, int N);
+int dkt_mll_rownoise_f32(const float* E, long e_batch_stride, long e_class_stride, const float* Y, long y_batch_stride,
+                         const float* noise_rows, long nr_batch_stride, const float* sv, const float* mean, const float* cls_weight,
+                         float* logp, float* alpha, float* dE, float* dsv, float* dmean, float* chol, int* info, int B, int C, int N,
+                         unsigned flags, void* workspace, size_t workspace_bytes, void* stream);
+int dkt_dirichlet_proba_f32(const float* mu, const float* var, const float* eps, float* prob, int32_t* labels, int B, int C, int M,
+                            int S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
