@@ -86,6 +86,10 @@ SIGNATURES = {
     "dkt_mll_rownoise_f32": (_c_i, [_c_p, ctypes.c_long, ctypes.c_long, _c_p, ctypes.c_long, _c_p, ctypes.c_long] + [_c_p] * 10 + [_c_i, _c_i, _c_i, ctypes.c_uint,
                                     _c_p, ctypes.c_size_t, _c_p]),
     "dkt_dirichlet_proba_f32": (_c_i, [_c_p] * 5 + [_c_i, _c_i, _c_i, _c_i, _c_p]),
+    "dkt_rownoise_lowrank_state_bytes": (ctypes.c_size_t, [_c_i, _c_i]),
+    "dkt_rownoise_lowrank_f32": (_c_i, [_c_p, _c_p, ctypes.c_long, _c_p, ctypes.c_long] + [_c_p] * 9 + [ctypes.c_size_t, _c_i, _c_i, _c_i, _c_i, _c_p]),
+    "dkt_rownoise_lowrank_bwd_f32": (_c_i, [_c_p, _c_p, ctypes.c_long, _c_p, ctypes.c_long] + [_c_p] * 4 + [ctypes.c_size_t, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p]),
+    "dkt_rownoise_lowrank_predict_f32": (_c_i, [_c_p, _c_p, ctypes.c_size_t] + [_c_p] * 5 + [_c_i, _c_i, _c_i, _c_i, _c_p]),
 }
 LAPLACE_MAX_N, LAPLACE_MAX_C = 127, 32      # DKT_LAPLACE_MAX_N / _C of include/dkt_abi.h (DKT_ERR_SHAPE outside them): the limits of dkt_gpc_mode_f32,
                                             # and of dkt_mll_rownoise_f32 / dkt_dirichlet_proba_f32

@@ -219,7 +219,8 @@ class DKT(MetaTemplate):
             raise ValueError("likelihood must be one of %s, got %r" % (LIKELIHOODS, likelihood))
         # "gaussian": regression on +-1 labels (the paper's method, the reference's only objective); "bernoulli": the Laplace approximation of the log marginal
         # likelihood under a Bernoulli likelihood (docs/LAPLACE.md "Training"; up to 127 rows per episode); "dirichlet": the exact marginal likelihood of the class
-        # labels as Gaussian targets with a fixed noise per row (docs/DIRICHLET.md; up to 127 rows).  Not a module, parameter or buffer: the state dict is the same
+        # labels as Gaussian targets with a fixed noise per row (docs/DIRICHLET.md; up to 127 rows, any number with the linear kernels on up to 64
+        # features).  Not a module, parameter or buffer: the state dict is the same
         self.likelihood_type = likelihood
         self.kernel_type = configs.kernel_type if kernel_type is None else kernel_type
         # mixed-precision backbone (opt-in): "bf16" runs the backbone under torch.autocast up to, not including, bn_out; the GP head stays fp32.
@@ -311,7 +312,16 @@ class DKT(MetaTemplate):
         if c > ops._lib.LAPLACE_MAX_C:
             raise ValueError("likelihood='%s' takes up to %d classes, the episode has %d" % (likelihood, ops._lib.LAPLACE_MAX_C, c))
         if n > ops._lib.LAPLACE_MAX_N:
-            raise ValueError("likelihood='%s' takes episodes of up to %d rows (%s), this one has %d" % (likelihood, ops._lib.LAPLACE_MAX_N, rows, n))
+            more = ("; larger ones run in feature space: linear / cossim / bncossim with up to %d features (a multiple of 4), on the GPU" % ops.LOWRANK_DP
+                    if likelihood == "dirichlet" else "")
+            raise ValueError("likelihood='%s' takes episodes of up to %d rows (%s), this one has %d%s" % (likelihood, ops._lib.LAPLACE_MAX_N, rows, n, more))
+
+    def _dirichlet_in_feature_space(self, z, c, shape=None):
+        """Does a Dirichlet episode on the rows z [.., N, D] (or, before they exist, of rows of shape (N, D) on the device of z) run in feature space
+        (ops.rownoise_lowrank_*: the linear kernels, D <= 64, rows on the GPU; by default above the 127 rows of the resident kernel)?  The ONE statement of
+        the route: the loss, the conditioning and the fused evaluation all ask here."""
+        n, d = z.shape[-2:] if shape is None else shape
+        return self.kernel_type in LINEAR_KINDS and ops.rownoise_lowrank_applies(int(n), int(d), c, z.is_cuda)
 
     def _dirichlet_targets(self, y):
         """(ytilde, noise_rows) of the +-1 one-vs-rest targets y (ops.dirichlet_targets), built once per target tensor of `_targets`."""
@@ -322,14 +332,18 @@ class DKT(MetaTemplate):
             self._target_cache[key] = t
         return t[0], t[1]
 
-    def _condition(self, e, y, sv, mean, noise):
+    def _condition(self, e, y, sv, mean, noise, rows=None):
         """The mean cache (alpha) of the class models on a conditioning set with base matrix e and +-1 targets y, under the model's likelihood: the Gaussian
-        posterior of ops.mll, or -- likelihood="dirichlet" -- that of the transformed labels with their noise per row (ops.mll_rownoise; no jitter ladder)."""
+        posterior of ops.mll, or -- likelihood="dirichlet" -- that of the transformed labels with their noise per row (ops.mll_rownoise; no jitter ladder).
+        rows [B,N,D] in the place of e (None): the Dirichlet posterior in feature space (ops.rownoise_lowrank), whose `state` ops.rownoise_lowrank_predict reads."""
         if self.likelihood_type != "dirichlet":
             return ops.mll(e, y, sv, mean, noise, jitter0=self.jitter0, max_tries=self.max_tries)
-        self._check_resident_rows(e.shape[-1], y.shape[-2], "dirichlet", "the conditioning set")
         yt, nr = self._dirichlet_targets(y)
-        out = ops.mll_rownoise(e, yt, nr, sv, mean)
+        if rows is not None:
+            out = ops.rownoise_lowrank(rows, yt, nr, sv, mean)
+        else:
+            self._check_resident_rows(e.shape[-1], y.shape[-2], "dirichlet", "the conditioning set")
+            out = ops.mll_rownoise(e, yt, nr, sv, mean)
         out["jitter"] = torch.zeros_like(out["logp"])
         return out
 
@@ -422,7 +436,8 @@ class DKT(MetaTemplate):
                 eps=1e-5 if bn is None else bn.eps, use_bn=bn is not None)
             alpha, jit, info = None, None, torch.zeros_like(iters)      # (B = I + W^1/2 K W^1/2 has eigenvalues >= 1: no jitter ladder, nothing can fail)
         elif self.likelihood_type == "dirichlet":
-            self._check_resident_rows(n, c, "dirichlet")
+            if not self._dirichlet_in_feature_space(xb, c):
+                self._check_resident_rows(n, c, "dirichlet")
             yt, nr = self._dirichlet_targets(y)
             obj, logp, alpha, info, e, bmean, bvar, a, s, rnorm = ops.episode_loss_dirichlet_bn(
                 xb, None if bn is None else bn.weight, None if bn is None else bn.bias, yt, nr, sv, mean, cw,
@@ -486,11 +501,12 @@ class DKT(MetaTemplate):
         if self.likelihood_type == "dirichlet":
             # minimise -(1/C) sum_c logp_c / N of the C = n_way exact GPs on the transformed labels (the same scaling); outputscale and the constant mean train, the
             # noise is the likelihood's own per row and the frozen Gaussian noise does not enter
-            self._check_resident_rows(n, c, "dirichlet")
+            if not self._dirichlet_in_feature_space(zb, c):
+                self._check_resident_rows(n, c, "dirichlet")
             yt, nr = self._dirichlet_targets(y)
             obj, logp, alpha, info, e = ops.episode_loss_dirichlet(zb, yt, nr, sv, mean, cw, self.kernel_type, self.model.lengthscale, self.model.offset,
                                                                    unit_rows=bool(self.normalize))
-            return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=None, e=e.detach())
+            return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=None, e=None if e is None else e.detach())      # (no E in feature space)
         if self.kernel_type in LINEAR_KINDS:
             obj, logp, alpha, info, jit, e = ops.episode_loss_linear(zb, y, sv, mean, noise, cw, self.jitter0, self.max_tries,
                                                                      unit_rows=bool(self.normalize))
@@ -524,6 +540,10 @@ class DKT(MetaTemplate):
         sv, mean, noise, ls, off = self._hypers_detached()
         zc = z_cond.detach().unsqueeze(0)
         zs = z_star.detach().unsqueeze(0)
+        if self.likelihood_type == "dirichlet" and self._dirichlet_in_feature_space(zc, y.shape[-2]):
+            out = self._condition(None, y, sv, mean, noise, rows=zc.float())
+            mu, _, labels = ops.rownoise_lowrank_predict(zs.float(), out["state"], sv, mean)
+            return mu[0], labels[0], out
         if self.kernel_type in LINEAR_KINDS:
             if e_cond is None:
                 e_cond = ops.kernel_matrix(zc, None, self.kernel_type)
@@ -558,6 +578,9 @@ class DKT(MetaTemplate):
         bn = self._bn_out(True)
         if self.feature_extractor.training or (bn is not None and not bn.track_running_stats):
             return None
+        if self.likelihood_type == "dirichlet" and self._dirichlet_in_feature_space(
+                x_support, y.shape[-2], (ns, int(np.prod(self.feature_extractor.final_feat_dim)))):
+            return None                                       # (no E of the support set: the unfused path conditions in feature space, before any trunk pass)
         x_feat = self._trunk_features(torch.cat([x_support, x_query], 0)).detach()
         d = x_feat.shape[1]
         if x_feat.dim() != 2 or not self._fused_front_end(ns + nq, d):
@@ -849,7 +872,6 @@ class DKT(MetaTemplate):
         self._check_way(self.n_way)
         xd = self._upload(x if batched else x.unsqueeze(0))
         ns, nq = self.n_way * self.n_support, self.n_way * (xd.shape[2] - self.n_support)
-        self._check_resident_rows(ns, self.n_way, "dirichlet", "n_way * n_support")
         with torch.no_grad():
             self._mode(False)
             z = torch.stack([self._embed(torch.cat([xe[:, :self.n_support].reshape(ns, *xe.shape[2:]), xe[:, self.n_support:].reshape(nq, *xe.shape[2:])], 0))
@@ -857,6 +879,10 @@ class DKT(MetaTemplate):
             zs, zq = z[:, :ns].contiguous(), z[:, ns:].contiguous()
             sv, mean, _, ls, off = self._hypers_detached()
             yt, nr = self._dirichlet_targets(self._targets(self.n_way, self.n_support, z.device))
+            if self._dirichlet_in_feature_space(zs, self.n_way):          # (more than 127 support rows: the D x D models, the latent variance from their state)
+                out = ops.rownoise_lowrank(zs, yt, nr, sv, mean)
+                return ops.rownoise_lowrank_predict(zq, out["state"], sv, mean)[:2]
+            self._check_resident_rows(ns, self.n_way, "dirichlet", "n_way * n_support")
             zero = torch.zeros_like(sv)                       # the LATENT variance: no observation noise on the queries
             if self.kernel_type in LINEAR_KINDS:
                 ex = ops.kernel_matrix(zq, zs, self.kernel_type)

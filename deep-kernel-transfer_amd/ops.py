@@ -1007,6 +1007,102 @@ def _lowrank_backward(z, v, t, wd, gobj) -> torch.Tensor:
     return dz
 
 
+# ---- the Dirichlet likelihood in feature space (include/dkt_abi.h "dkt_rownoise_lowrank_*", csrc/dkt_mll_rownoise.hip; docs/DIRICHLET.md) ----
+ROWNOISE_LOWRANK_STATE = LOWRANK_DP * (LOWRANK_DP + 1)      # floats per (episode, class) of the opaque state: t [DP], B^-1 [DP,DP]
+
+
+def rownoise_lowrank_supported(n: int, d: int, c: int) -> bool:
+    """Shapes the feature-space row-noise calls take: K_c = sv_c Z Z^T + diag(noise_rows_c) with D <= 64, D % 4 == 0, C <= 32, any number of rows."""
+    return n >= 1 and 1 <= d <= LOWRANK_DP and d % 4 == 0 and 1 <= c <= _lib.LAPLACE_MAX_C
+
+
+def rownoise_lowrank_applies(n: int, d: int, c: int, on_gpu: bool = True) -> bool:
+    """Does a Dirichlet episode of the linear kernels run in feature space?  DKT_DIRICHLET_LOWRANK: 1 (default) = above the 127 rows of the resident kernel;
+    0 = never; force = wherever the shape is supported (tests: against the resident kernel below 128 rows).  Only for rows on the GPU."""
+    mode = os.environ.get("DKT_DIRICHLET_LOWRANK", "1")
+    if mode == "0" or not on_gpu or not rownoise_lowrank_supported(n, d, c):
+        return False
+    return mode == "force" or n > _lib.LAPLACE_MAX_N
+
+
+def _rownoise_lowrank_args(z, y, noise_rows, sv, mean, cls_weight, what):
+    z = _req(z, "z", 3)
+    b_, n, d = z.shape
+    y = _req(y, "y", y.dim() if y.dim() in (2, 3) else 2)
+    noise_rows = _req(noise_rows, "noise_rows", noise_rows.dim() if noise_rows.dim() in (2, 3) else 2)
+    c_ = y.shape[-2]
+    if (y.shape[-1] != n or tuple(noise_rows.shape[-2:]) != (c_, n) or (y.dim() == 3 and y.shape[0] != b_)
+            or (noise_rows.dim() == 3 and noise_rows.shape[0] != b_)):
+        raise RuntimeError("%s: z must be [B,N,D] and y, noise_rows [C,N] or [B,C,N], got %s, %s and %s"
+                           % (what, tuple(z.shape), tuple(y.shape), tuple(noise_rows.shape)))
+    sv = _req(sv.reshape(-1), "sv", 1)
+    mean = _req(mean.reshape(-1), "mean", 1)
+    cw = None if cls_weight is None else _req(cls_weight.reshape(-1), "cls_weight", 1)
+    if not (sv.numel() == mean.numel() == c_) or (cw is not None and cw.numel() != c_):
+        raise RuntimeError("%s: sv / mean / cls_weight must have C=%d elements" % (what, c_))
+    return z, y, noise_rows, sv, mean, cw, (b_, c_, n, d)
+
+
+def rownoise_lowrank(z: torch.Tensor, y: torch.Tensor, noise_rows: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor,
+                     cls_weight: Optional[torch.Tensor] = None, want_grad: bool = False) -> dict:
+    """`mll_rownoise` for the linear kernels on the rows themselves, K_c = sv_c Z Z^T + diag(noise_rows_c) (dkt_rownoise_lowrank_f32; D <= 64, any N: no
+    N x N matrix exists).  z: [B,N,D]; y, noise_rows: [C,N] or [B,C,N]; sv, mean: C elements.
+    Returns dict(logp [B,C] unweighted, alpha [B,C,N], info [B,C] int32, state (opaque: what `rownoise_lowrank_bwd` / `rownoise_lowrank_predict` read), and
+    with want_grad dsv = cls_weight_c d logp / d sv_c, dmean = cls_weight_c sum alpha [B,C])."""
+    z, y, noise_rows, sv, mean, cw, (b_, c_, n, d) = _rownoise_lowrank_args(z, y, noise_rows, sv, mean, cls_weight, "rownoise_lowrank")
+    dev = z.device
+    logp = torch.empty((b_, c_), device=dev, dtype=torch.float32)
+    alpha = torch.empty((b_, c_, n), device=dev, dtype=torch.float32)
+    info = torch.empty((b_, c_), device=dev, dtype=torch.int32)
+    state = torch.empty((b_, c_, ROWNOISE_LOWRANK_STATE), device=dev, dtype=torch.float32)
+    dsv = torch.empty((b_, c_), device=dev, dtype=torch.float32) if want_grad else None
+    dmean = torch.empty((b_, c_), device=dev, dtype=torch.float32) if want_grad else None
+    with _timed("dkt_rownoise_lowrank_f32"):
+        st = _lib_now().dkt_rownoise_lowrank_f32(_p(z), _p(y), c_ * n if y.dim() == 3 else 0, _p(noise_rows), c_ * n if noise_rows.dim() == 3 else 0, _p(sv),
+                                                 _p(mean), _p(cw), _p(logp), _p(alpha), _p(info), _p(dsv), _p(dmean), _p(state), state.numel() * 4,
+                                                 b_, c_, n, d, _stream())
+    _lib.check(st, "dkt_rownoise_lowrank_f32")
+    return dict(logp=logp, alpha=alpha, info=info, state=state, dsv=dsv, dmean=dmean)
+
+
+def rownoise_lowrank_bwd(z, y, noise_rows, sv, mean, cls_weight, state: torch.Tensor, gobj: torch.Tensor) -> torch.Tensor:
+    """dZ [B,N,D] of sum_b gobj[b] sum_c cls_weight[c] logp[b,c] from the state `rownoise_lowrank` left (dkt_rownoise_lowrank_bwd_f32: the classes in
+    index order, no atomics)."""
+    z, y, noise_rows, sv, mean, cw, (b_, c_, n, d) = _rownoise_lowrank_args(z, y, noise_rows, sv, mean, cls_weight, "rownoise_lowrank_bwd")
+    state = _req(state, "state", 3)
+    gobj = _req(gobj.reshape(-1), "gobj", 1)
+    if tuple(state.shape) != (b_, c_, ROWNOISE_LOWRANK_STATE) or gobj.numel() != b_:
+        raise RuntimeError("rownoise_lowrank_bwd: state must be the [%d,%d,%d] of rownoise_lowrank and gobj [%d]" % (b_, c_, ROWNOISE_LOWRANK_STATE, b_))
+    dz = torch.empty_like(z)
+    with _timed("dkt_rownoise_lowrank_bwd_f32"):
+        st = _lib_now().dkt_rownoise_lowrank_bwd_f32(_p(z), _p(y), c_ * n if y.dim() == 3 else 0, _p(noise_rows), c_ * n if noise_rows.dim() == 3 else 0,
+                                                     _p(sv), _p(mean), _p(cw), _p(state), state.numel() * 4, _p(gobj), _p(dz), b_, c_, n, d, _stream())
+    _lib.check(st, "dkt_rownoise_lowrank_bwd_f32")
+    return dz
+
+
+def rownoise_lowrank_predict(zq: torch.Tensor, state: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor):
+    """The latent posterior of the class models at the queries zq [B,M,D] from the state of `rownoise_lowrank` on the conditioning rows
+    (dkt_rownoise_lowrank_predict_f32): (mu [B,C,M], var [B,C,M] without observation noise, labels [B,M] int32 = argmax_c mu, the first maximum)."""
+    zq = _req(zq, "zq", 3)
+    state = _req(state, "state", 3)
+    b_, m, d = zq.shape
+    c_ = state.shape[1]
+    sv = _req(sv.reshape(-1), "sv", 1)
+    mean = _req(mean.reshape(-1), "mean", 1)
+    if state.shape[0] != b_ or state.shape[2] != ROWNOISE_LOWRANK_STATE or not (sv.numel() == mean.numel() == c_):
+        raise RuntimeError("rownoise_lowrank_predict: state must be the [B=%d,C,%d] of rownoise_lowrank and sv, mean have C elements, got %s, %d and %d"
+                           % (b_, ROWNOISE_LOWRANK_STATE, tuple(state.shape), sv.numel(), mean.numel()))
+    mu = torch.empty((b_, c_, m), device=zq.device, dtype=torch.float32)
+    var = torch.empty((b_, c_, m), device=zq.device, dtype=torch.float32)
+    labels = torch.empty((b_, m), device=zq.device, dtype=torch.int32)
+    with _timed("dkt_rownoise_lowrank_predict_f32"):
+        st = _lib_now().dkt_rownoise_lowrank_predict_f32(_p(zq), _p(state), state.numel() * 4, _p(sv), _p(mean), _p(mu), _p(var), _p(labels), b_, c_, m, d,
+                                                         _stream())
+    _lib.check(st, "dkt_rownoise_lowrank_predict_f32")
+    return mu, var, labels
+
+
 # ------------------------------------------------------------------------------------------------------
 # BNCosSim front half fused into the Gram build (reference methods/DKT.py:48,141-142,375-378)
 # ------------------------------------------------------------------------------------------------------
@@ -1259,8 +1355,31 @@ class _Dirichlet:
 
     @staticmethod
     def backward(saved, shapes, gobj, need_y, need_noise_rows, need_sv, need_mean, *_):
-        _, dsv, dmean = saved                                                     # (both carry cls_weight already)
+        _, dsv, dmean, *_ = saved                                                 # (both carry cls_weight already)
         return (None, None, _sum_episodes(gobj, dsv, shapes[0]) if need_sv else None, _sum_episodes(gobj, dmean, shapes[1]) if need_mean else None, None)
+
+
+class _FeatureSpaceDirichlet(_Dirichlet):
+    """The same objective for the linear kernels in feature space (D <= 64, any N), on the rows Z and not on E: the D x D models B_c = I + sv_c Z^T
+    diag(noise_rows_c)^-1 Z in ONE call (dkt_rownoise_lowrank_f32), dZ from the state it leaves (dkt_rownoise_lowrank_bwd_f32).  Neither E nor dE is ever
+    formed: the 20-way episodes of 400 / 420 rows."""
+    on_features, resident_only = True, False
+    de = None
+
+    @staticmethod
+    def forward(rows, ytilde, noise_rows, sv, mean, cls_weight):
+        z, _ = rows
+        with torch.no_grad():
+            out = rownoise_lowrank(z, ytilde, noise_rows, sv, mean, cls_weight, want_grad=True)
+            obj = objective(out["logp"], cls_weight)
+            kept = (ytilde.contiguous(), noise_rows.contiguous(), sv.reshape(-1).contiguous(), mean.reshape(-1).contiguous(),
+                    None if cls_weight is None else cls_weight.reshape(-1).contiguous())
+        return obj, (out["logp"], out["alpha"], out["info"]), (out["state"], out["dsv"], out["dmean"]) + kept, (sv.shape, mean.shape)
+
+    @staticmethod
+    def drows(z, saved, gobj):
+        state, _, _, ytilde, noise_rows, sv, mean, cw = saved
+        return rownoise_lowrank_bwd(z, ytilde, noise_rows, sv, mean, cw, state, gobj)
 
 
 def _rows_grad(objv, osaved, z, gobj, unit_rows):
@@ -1449,19 +1568,23 @@ def dirichlet_objective(e, ytilde, noise_rows, sv, mean, cls_weight):
 
 
 def episode_loss_dirichlet(z, ytilde, noise_rows, sv, mean, cls_weight, kernel: str, lengthscale=None, offset=None, unit_rows: bool = False):
-    """Dirichlet-likelihood training episode(s) z [B,N,D] (N <= 127, C <= 32): K_c = sv_c * k_c(z, z) + diag(noise_rows_c).
+    """Dirichlet-likelihood training episode(s) z [B,N,D] (N <= 127, C <= 32): K_c = sv_c * k_c(z, z) + diag(noise_rows_c).  The linear kernels with
+    D <= 64 take any N: above 127 rows (rownoise_lowrank_applies) the episode runs in feature space and E is None.
     Returns (obj [B], logp [B,C], alpha [B,C,N], info [B,C], E)."""
     z = _req(z, "z", 3)
     if kernel in LINEAR_KINDS:
-        return _EpisodeFn.apply(_LinearGram, _Dirichlet, z, unit_rows, ytilde, noise_rows, sv, mean, cls_weight)
+        objv = _FeatureSpaceDirichlet if rownoise_lowrank_applies(z.shape[1], z.shape[2], ytilde.shape[-2], z.is_cuda) else _Dirichlet
+        return _EpisodeFn.apply(_LinearGram, objv, z, unit_rows, ytilde, noise_rows, sv, mean, cls_weight)
     cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
     return _EpisodeFn.apply(_ClassKernel, _Dirichlet, z, param, cmap, power, base_kind, ytilde, noise_rows, sv, mean, cls_weight)
 
 
 def episode_loss_dirichlet_bn(x, gamma, beta, ytilde, noise_rows, sv, mean, cls_weight, eps: float = 1e-5, use_bn: bool = True):
-    """x [B,N,D] trunk output BEFORE bn_out (float32, bfloat16 or float16), N <= 127.
+    """x [B,N,D] trunk output BEFORE bn_out (float32, bfloat16 or float16), N <= 127 -- or, with D <= 64, any N: above 127 rows the episode runs in
+    feature space (rownoise_lowrank_applies) and E is None.
     Returns (obj [B], logp, alpha, info, E, batch_mean, batch_var_unbiased, a, s, rnorm)."""
-    return _EpisodeFn.apply(_BnTrunk, _Dirichlet, x, gamma, beta, eps, use_bn, ytilde, noise_rows, sv, mean, cls_weight)
+    objv = _FeatureSpaceDirichlet if x.dim() == 3 and rownoise_lowrank_applies(x.shape[1], x.shape[2], ytilde.shape[-2], x.is_cuda) else _Dirichlet
+    return _EpisodeFn.apply(_BnTrunk, objv, x, gamma, beta, eps, use_bn, ytilde, noise_rows, sv, mean, cls_weight)
 
 
 def episode_loss_class_kernel(z, y, sv, mean, noise, cls_weight, kernel: str, lengthscale=None, offset=None,

@@ -453,6 +453,38 @@ int dkt_mll_rownoise_f32(const float* E, long e_batch_stride, long e_class_strid
 int dkt_dirichlet_proba_f32(const float* mu, const float* var, const float* eps, float* prob, int32_t* labels, int B, int C, int M,
                             int S, void* stream);
 
+/*
+ * ---- the Dirichlet likelihood in FEATURE space: linear kernels, D <= DKT_LOWRANK_DP, any N (additive entries of ABI 7; docs/DIRICHLET.md) ----
+ * K_c = sv[c] Z Z^T + diag(noise_rows_c) is never formed.  Per problem (b, c), with s = sv[c], Lambda = diag(noise_rows_c), r = y_c - mean[c]:
+ *     B = I + s Z^T Lambda^-1 Z  (D x D, every eigenvalue >= 1: no jitter ladder),  u = Z^T Lambda^-1 r,  t = B^-1 u = Z^T alpha
+ *     alpha = Lambda^-1 (r - s Z t),  logp = -1/2 (r.Lambda^-1 r - s u.t) - 1/2 (sum log noise_rows + log det B) - N/2 log 2 pi
+ * Z:[B,N,D] row-major and 16-byte aligned, D % 4 == 0, D <= DKT_LOWRANK_DP (zero-padded to it), 1 <= C <= DKT_LAPLACE_MAX_C, any N >= 1, any M >= 1
+ * (DKT_ERR_SHAPE otherwise, before any launch; a NULL or misaligned pointer: DKT_ERR_BAD_ARG, before the shape test).  Y, noise_rows, sv, mean, cls_weight
+ * and their strides as in dkt_mll_rownoise_f32.  `state` is an opaque buffer of dkt_rownoise_lowrank_state_bytes(B, C) bytes (DKT_ERR_WORKSPACE when
+ * state_bytes is less), 16-byte aligned: t_c and B_c^-1 per problem, written by the first call and read by the other two.
+ *
+ * dkt_rownoise_lowrank_f32 -- logp [B,C] (unweighted), alpha [B,C,N], info [B,C] (0, or 1 + the index of a pivot of B that is not finite and positive:
+ *   NaN outputs and a NaN state for that problem), dsv [B,C] = cls_weight[c] 1/2 (|t|^2 - (D - tr B^-1) / s), dmean [B,C] = cls_weight[c] sum_i alpha_i
+ *   (either may be NULL), and the state.
+ * dkt_rownoise_lowrank_bwd_f32 -- dZ [B,N,D] = gobj[b] sum_c cls_weight[c] s_c Lambda_c^-1 (r_c t_c^T - Z Q_c), Q_c = s_c t_c t_c^T + B_c^-1: the gradient
+ *   of sum_b gobj[b] sum_c cls_weight[c] logp[b,c] in Z.  The classes are summed in index order, no atomics: two runs give the same bits.
+ * dkt_rownoise_lowrank_predict_f32 -- the latent posterior at the queries Zq [B,M,D]: mu [B,C,M] = mean[c] + s z.t_c, var [B,C,M] = s z^T B_c^-1 z (no
+ *   observation noise), labels [B,M] (may be NULL) = argmax_c mu, the first maximum wins as in dkt_predict_f32.
+ * Plain fp32 on the VALU, passes 1 to 3 of the kernel of dkt_dirichlet_proba_f32 (no kernel instance of their own; the kernel of
+ * dkt_mll_rownoise_f32 is untouched); no host read-back.
+ * Replaces what dkt_mll_rownoise_f32 replaces (methods/DKT.py:161-163 under a DirichletClassificationLikelihood) on episodes of any number of rows --
+ * the 20-way episodes of 400 / 420 rows -- and at test time the conditioning and prediction of methods/DKT.py:237-240, 258-270.
+ */
+size_t dkt_rownoise_lowrank_state_bytes(int B, int C);
+int dkt_rownoise_lowrank_f32(const float* Z, const float* Y, long y_batch_stride, const float* noise_rows, long nr_batch_stride, const float* sv,
+                             const float* mean, const float* cls_weight, float* logp, float* alpha, int* info, float* dsv, float* dmean, void* state,
+                             size_t state_bytes, int B, int C, int N, int D, void* stream);
+int dkt_rownoise_lowrank_bwd_f32(const float* Z, const float* Y, long y_batch_stride, const float* noise_rows, long nr_batch_stride, const float* sv,
+                                 const float* mean, const float* cls_weight, const void* state, size_t state_bytes, const float* gobj, float* dZ, int B,
+                                 int C, int N, int D, void* stream);
+int dkt_rownoise_lowrank_predict_f32(const float* Zq, const void* state, size_t state_bytes, const float* sv, const float* mean, float* mu, float* var,
+                                     int32_t* labels, int B, int C, int M, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
