@@ -1,5 +1,5 @@
 """The training-episode routes of dkt_amd.ops, each defined once: how E is made (given, linear Gram, contraction + class kernel, the BN trunk front end in its
-resident and big forms) times what is solved on it (Gaussian marginal likelihood, its feature-space form, Laplace).  A route is a name, the environment it
+resident and big forms) times what is solved on it (Gaussian marginal likelihood, its feature-space form, Laplace, Dirichlet and its feature-space form).  A route is a name, the environment it
 needs, a callable that builds seeded inputs and returns (leaves, call), and the library launches its forward and backward make, in order.  `run` executes one:
 forward, backward with a seeded upstream gradient, every output and every leaf gradient returned -- and, with `launches=True`, the launches of each half as
 ops.kernel_timing records them.  tests/test_episode_routes_gpu.py pins the launch lists; the same routes serve bit-for-bit comparisons between two commits."""
@@ -98,15 +98,43 @@ def laplace_bn(dev):
     return dict(x=x, gamma=gamma, beta=beta, sv=sv), lambda: ops.episode_loss_laplace_bn(x, gamma, beta, _targets(25, dev, True), sv, cw)
 
 
+def _dirichlet_targets(n, dev):
+    return ops.dirichlet_targets(_targets(n, dev))
+
+
+def dirichlet_objective(dev):
+    e = _given_e(dev)
+    sv, mean, _, cw = _hypers(dev, 25)
+    return dict(e=e, sv=sv, mean=mean), lambda: ops.dirichlet_objective(e, *_dirichlet_targets(25, dev), sv, mean, cw)
+
+
+def dirichlet(dev, kernel, n=25):
+    z = _features(n, 64, dev)
+    sv, mean, _, cw = _hypers(dev, n)
+    ls = _leaf(torch.tensor([0.6, 0.8, 1.0, 1.2, 0.9]), dev)
+    leaves = dict(z=z, sv=sv, mean=mean, **(dict(lengthscale=ls) if kernel == "rbf" else {}))
+    return leaves, lambda: ops.episode_loss_dirichlet(z, *_dirichlet_targets(n, dev), sv, mean, cw, kernel, lengthscale=ls, unit_rows=kernel != "rbf")
+
+
+def dirichlet_bn(dev, n=25, d=64, use_bn=True, dtype=torch.float32):
+    x, gamma, beta = _trunk(n, d, dev, dtype)
+    sv, mean, _, cw = _hypers(dev, n)
+    leaves = dict(x=x, sv=sv, mean=mean, **(dict(gamma=gamma, beta=beta) if use_bn else {}))
+    return leaves, lambda: ops.episode_loss_dirichlet_bn(x, gamma if use_bn else None, beta if use_bn else None, *_dirichlet_targets(n, dev), sv, mean, cw,
+                                                         use_bn=use_bn)
+
+
 class Route:
-    def __init__(self, name, build, forward, backward, env=None, e_is_none=False):
-        self.name, self.build, self.env, self.e_is_none = name, build, env or {}, e_is_none
+    def __init__(self, name, build, forward, backward, env=None, e_is_none=False, e_index=5):
+        self.name, self.build, self.env, self.e_is_none, self.e_index = name, build, env or {}, e_is_none, e_index      # e_index: where E is among the outputs
         self.forward, self.backward = ["dkt_%s" % k for k in forward.split()], ["dkt_%s" % k for k in backward.split()]
 
 
 _MLL = "mll_f32 objective_f32"
 _LAPLACE = "gpc_mode_f32 laplace_grad_f32 objective_f32"
 _LOWRANK = "lowrank_gram_f32 mll_f32 lowrank_finish_f32"
+_DIRICHLET = "mll_rownoise_f32 objective_f32"
+_DIRICHLET_LOWRANK = "rownoise_lowrank_f32 objective_f32"
 _BN_BWD = "gram_bn_bwd_f32 bn_param_grads_f32"
 ROUTES = [
     Route("mll_objective", mll_objective, _MLL, "hyper_grads_f32"),
@@ -126,6 +154,16 @@ ROUTES = [
     Route("laplace-linear", lambda dev: laplace(dev, "bncossim"), "gram_f32 " + _LAPLACE, "gram_bwd_f32"),
     Route("laplace-rbf", lambda dev: laplace(dev, "rbf"), "gram_f32 class_kernel_f32 " + _LAPLACE, "class_kernel_bwd_f32 gram_bwd_f32"),
     Route("laplace-bn", laplace_bn, "gram_bn_train_f32 " + _LAPLACE, _BN_BWD),
+    Route("dirichlet-objective", dirichlet_objective, _DIRICHLET, "", e_index=None),
+    Route("dirichlet-linear", lambda dev: dirichlet(dev, "bncossim"), "gram_f32 " + _DIRICHLET, "gram_bwd_f32", e_index=4),
+    Route("dirichlet-class-kernel-rbf", lambda dev: dirichlet(dev, "rbf"), "gram_f32 class_kernel_f32 " + _DIRICHLET, "class_kernel_bwd_f32 gram_bwd_f32", e_index=4),
+    Route("dirichlet-bn-resident", dirichlet_bn, "gram_bn_train_f32 " + _DIRICHLET, _BN_BWD, e_index=4),
+    Route("dirichlet-bn-resident-no-bn", lambda dev: dirichlet_bn(dev, use_bn=False), "gram_bn_f32 " + _DIRICHLET, "gram_bn_bwd_f32", e_index=4),
+    Route("dirichlet-bn-resident-bf16", lambda dev: dirichlet_bn(dev, dtype=torch.bfloat16), "gram_bn_train_x16 " + _DIRICHLET,
+          "gram_bn_bwd_x16 bn_param_grads_f32", e_index=4),
+    Route("dirichlet-linear-feature-space", lambda dev: dirichlet(dev, "bncossim", n=130), _DIRICHLET_LOWRANK, "rownoise_lowrank_bwd_f32", e_is_none=True, e_index=4),
+    Route("dirichlet-bn-feature-space", lambda dev: dirichlet_bn(dev, n=130, d=64), "bn_stats_f32 affine_normalize_f32 " + _DIRICHLET_LOWRANK,
+          "rownoise_lowrank_bwd_f32 normalize_bn_bwd_f32 bn_param_grads_f32", e_is_none=True, e_index=4),
     # gradients nobody asked for skip their launches
     Route("linear-only-sv", lambda dev: linear(dev, z_grad=False, only_sv=True), "gram_f32 " + _MLL, "hyper_grads_f32"),
     Route("class-kernel-hypers-only", lambda dev: class_kernel(dev, "rbf", grads=False), "gram_f32 class_kernel_f32 " + _MLL, "hyper_grads_f32"),
