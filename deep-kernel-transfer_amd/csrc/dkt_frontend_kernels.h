@@ -893,7 +893,14 @@ __global__ __launch_bounds__(64 * NT, DKT_FE_BWD_WPE) void gram_bn_bwd_ep_kernel
         // VALU instructions of what the phase clocks show to be the heaviest part of a slab)
         const f32x2 a2[2] = {{ea.x, ea.y}, {ea.z, ea.w}}, s2[2] = {{es.x, es.y}, {es.z, es.w}};
         const f32x2 er2[2] = {{er.x, er.y}, {er.z, er.w}};
-        const f32x2 emer2[2] = {{-em.x * er.x, -em.y * er.y}, {-em.z * er.z, -em.w * er.w}};       // xh = x rstd - mean rstd
+        // xh = x rstd - mean rstd in ONE packed FMA per pair against the rounded product emer = -(mean rstd).  What that rounding drops, xc = -mean rstd - emer
+        // (exact, one FMA per feature), is a constant of the feature: xh = xhk + xc, so  sum dY xh = sum dY xhk + xc sum dY  and
+        // dbeta / N + xh dgamma / N = (dbeta / N + xc dgamma / N) + xhk dgamma / N -- two per-feature corrections behind the reduction instead of an
+        // instruction per row.  Without them the eps |mean| rstd of emer is what a two-row batch, whose dX is a 1e-5 remainder of dY, amplifies past the
+        // float32 floor (docs/FRONTEND_BWD.md); (x - mean) rstd in the row loop measured 8 - 16 % slower at NT >= 7.
+        const f32x2 emer2[2] = {{-em.x * er.x, -em.y * er.y}, {-em.z * er.z, -em.w * er.w}};
+        const f32x2 xc2[2] = {{__builtin_fmaf(-em.x, er.x, -emer2[0].x), __builtin_fmaf(-em.y, er.y, -emer2[0].y)},
+                              {__builtin_fmaf(-em.z, er.z, -emer2[1].x), __builtin_fmaf(-em.w, er.w, -emer2[1].y)}};
         f32x2 dy2[4][2], xh2[4][2];                     // [reg][feature pair]
         f32x2 c1p[2] = {{0.f, 0.f}, {0.f, 0.f}}, c2p[2] = {{0.f, 0.f}, {0.f, 0.f}};
 #pragma unroll
@@ -948,6 +955,8 @@ __global__ __launch_bounds__(64 * NT, DKT_FE_BWD_WPE) void gram_bn_bwd_ep_kernel
                 m1p[0] += (f32x2){p1[0], p1[1]}; m1p[1] += (f32x2){p1[2], p1[3]};
                 m2p[0] += (f32x2){p2[0], p2[1]}; m2p[1] += (f32x2){p2[2], p2[3]};
             }
+#pragma unroll
+            for (int p2 = 0; p2 < 2; ++p2) m2p[p2] += xc2[p2] * m1p[p2];      // dgamma = sum dY xhk + xc sum dY
             // (branch-free stores, round 5: lanes with nothing to store get an out-of-range offset -- behind a branch the compiler counts no store as
             // outstanding, and its `vmcnt(0)` in front of the next slab's operands drained these stores at the top of every trip; soffset stays 0)
             const int po = (wave == 0 && q == 0 && din) ? (d0 + 4 * r16) * 4 : OOB;
@@ -957,6 +966,7 @@ __global__ __launch_bounds__(64 * NT, DKT_FE_BWD_WPE) void gram_bn_bwd_ep_kernel
             for (int p2 = 0; p2 < 2; ++p2) {
                 m1p[p2] *= inv_n;
                 m2p[p2] *= inv_n;
+                m1p[p2] += xc2[p2] * m2p[p2];                             // the xc share of xh dgamma / N rides on dbeta / N
             }
         }
 #pragma unroll
