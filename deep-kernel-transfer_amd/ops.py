@@ -304,10 +304,24 @@ def gram_bwd(w: torch.Tensor, z: torch.Tensor, ep_scale: Optional[torch.Tensor] 
     return dz
 
 
-def rbf_bwd(w: torch.Tensor, e: torch.Tensor, lengthscale: torch.Tensor):
+def _req_distance_bwd(fn: str, w: torch.Tensor, m: torch.Tensor, mname: str, lengthscale: torch.Tensor):
+    """Arguments of rbf_bwd / sqdist_bwd: w and the forward's matrix of the same [B,N,N] shape (a smaller w would be read past its end), ONE lengthscale
+    (the kernels read element 0: a [C] tensor would silently mean class 0 -- per-class lengthscales go through class_kernel_bwd)."""
     w = _req(w, "w", 3)
-    e = _req(e, "e", 3)
-    lengthscale = _req(lengthscale.reshape(-1), "lengthscale", 1)
+    m = _req(m, mname, 3)
+    if not isinstance(lengthscale, torch.Tensor):
+        raise RuntimeError("%s: lengthscale must be a tensor" % fn)
+    if m.shape[1] != m.shape[2]:
+        raise RuntimeError("%s: %s must be [B,N,N], got %s" % (fn, mname, tuple(m.shape)))
+    if w.shape != m.shape:
+        raise RuntimeError("%s: w %s must have the shape of %s %s" % (fn, tuple(w.shape), mname, tuple(m.shape)))
+    if lengthscale.numel() != 1:
+        raise RuntimeError("%s: lengthscale must have one element (got %d); per-class lengthscales go through class_kernel_bwd" % (fn, lengthscale.numel()))
+    return w, m, _req(lengthscale.reshape(-1), "lengthscale", 1)
+
+
+def rbf_bwd(w: torch.Tensor, e: torch.Tensor, lengthscale: torch.Tensor):
+    w, e, lengthscale = _req_distance_bwd("rbf_bwd", w, e, "e", lengthscale)
     b_, n, _ = e.shape
     wp = torch.empty_like(e)
     dl = torch.empty((b_,), device=e.device, dtype=torch.float32)
@@ -319,9 +333,7 @@ def rbf_bwd(w: torch.Tensor, e: torch.Tensor, lengthscale: torch.Tensor):
 
 
 def sqdist_bwd(w: torch.Tensor, u: torch.Tensor, lengthscale: torch.Tensor):
-    w = _req(w, "w", 3)
-    u = _req(u, "u", 3)
-    lengthscale = _req(lengthscale.reshape(-1), "lengthscale", 1)
+    w, u, lengthscale = _req_distance_bwd("sqdist_bwd", w, u, "u", lengthscale)
     b_, n, _ = u.shape
     wp = torch.empty_like(u)
     dl = torch.empty((b_,), device=u.device, dtype=torch.float32)
