@@ -827,8 +827,8 @@ def class_kernel_bwd(w: torch.Tensor, base: torch.Tensor, cmap: int, power: int,
     base = _req(base, "base", 3)
     param = _req(param.reshape(-1), "param", 1)
     b_, c, n, _ = w.shape
-    if tuple(base.shape) != (b_, n, n) or param.numel() != c:
-        raise RuntimeError("class_kernel_bwd: base must be [B,N,N] and param [C]")
+    if tuple(w.shape) != (b_, c, n, n) or tuple(base.shape) != (b_, n, n) or param.numel() != c:          # (a w of fewer columns would be read past its end)
+        raise RuntimeError("class_kernel_bwd: w must be [B,C,N,N], base [B,N,N] and param [C]")
     wp = torch.empty_like(base)
     lib = _lib_now()
     nsplit = int(lib.dkt_class_kernel_bwd_nsplit(b_, n))

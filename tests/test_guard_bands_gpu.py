@@ -121,7 +121,7 @@ for _b, _n, _d in GRAM_SYM:
 
 
 # ------------------------------------------------------------------------------------------------ rbf_bwd, sqdist_bwd, class_kernel, class_kernel_bwd
-CK_N, CK_C = (7, 33, 128, 130, 258), (1, 5, 20, 32)
+CK_N, CK_C = (7, 33, 128, 130, 258, 131, 257), (1, 5, 20, 32)          # (131, 257: the 16-byte kernel of class_kernel_bwd at an odd N)
 CK_MAPS = dict(rbf=(ops.CLASSMAP_RBF, 0), matern=(ops.CLASSMAP_MATERN25, 0), poli1=(ops.CLASSMAP_POLY, 1), poli2=(ops.CLASSMAP_POLY, 2))
 
 
@@ -166,7 +166,8 @@ def _parts_summed_by_torch(b, n):
     return lambda: ("out[1]",) if int(_lib.load().dkt_class_kernel_bwd_nsplit(b, n)) > 1 else ()
 
 
-_ck = [(k, n, CK_C[(i + j) % 4]) for i, k in enumerate(CK_MAPS) for j, n in enumerate(CK_N)] + [(k, 33, c) for k in CK_MAPS for c in CK_C]
+_ck = [(k, n, CK_C[(i + j) % 4]) for i, k in enumerate(CK_MAPS) for j, n in enumerate(CK_N[:5])] + [(k, 33, c) for k in CK_MAPS for c in CK_C]
+_ck += [(k, n, CK_C[(i + j) % 4]) for i, k in enumerate(CK_MAPS) for j, n in enumerate(CK_N[5:])]          # (last: every earlier case keeps its B and its C)
 for _i, (_k, _n, _c) in enumerate(dict.fromkeys(_ck)):
     _b = (1, 3, 5)[_i % 3]
     case("class_kernel-%s-B%d-C%d-N%d" % (_k, _b, _c, _n), "dkt_class_kernel_f32", _class_kernel(_k, _b, _c, _n))
