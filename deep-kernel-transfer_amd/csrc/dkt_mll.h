@@ -29,17 +29,18 @@ struct MllArgs {
     unsigned flags;
     int p2_guard;                 // wave-per-episode kernel: binades of head room of the f16 scale of M over the diagonal tiles (DKT_MLL_P2_GUARD, default 1)
     float kappa_max = 0.f;        // f16-split kernels (dkt_mll_h2.hip): > 0 = a class whose a-priori bound 1 + sv trace(E) / noise exceeds it (and whose factorisation succeeded)
-                                  // leaves with info = -1 for the generic kernel's fix-up launch (dkt_mll.hip, mll_kappa_fixup); 0 = no test
+                                  // leaves with info = -1 for the generic kernel's fix-up launch (dkt_mll.hip, MllPlan::kappa_fixup); 0 = no test
 };
 
 constexpr float DKT_HALF_LOG_2PI = 0.91893853320467274178f;
 
-// Wave-per-class-matrix path on the f16 matrix pipe (dkt_mll_h2.hip): the default for N + 1 <= 128 unless the Cholesky factors are
-// requested.  Returns false when it does not apply.
-bool dkt_mll_h2_launch(const MllArgs& a, hipStream_t st);
-// The same structure on the exact-fp32 matrix instruction (dkt_mll_mfma.hip): DKT_MLL_FORCE_F32MFMA twin, and DKT_MLL_WANT_CHOL.
-// Returns false when N is out of range.
-bool dkt_mll_mfma_launch(const MllArgs& a, hipStream_t st);
+// Every path: a predicate (_serves / _applies / _supports) that mll_plan() of dkt_mll.hip consults, and a launcher that gets only what its predicate admitted.
+// Wave-per-class-matrix path on the f16 matrix pipe (dkt_mll_h2.hip): the default for N + 1 <= 128 unless the Cholesky factors or exact fp32 are requested.
+bool dkt_mll_h2_serves(int N, unsigned flags);
+void dkt_mll_h2_launch(const MllArgs& a, hipStream_t st);
+// The same structure on the exact-fp32 matrix instruction (dkt_mll_mfma.hip): WANT_CHOL up to N = 31; twins library: every N + 1 <= 128 (FORCE_F32MFMA twin, WANT_CHOL).
+bool dkt_mll_mfma_serves(int N, unsigned flags);
+void dkt_mll_mfma_launch(const MllArgs& a, hipStream_t st);
 // Register-resident sweep (dkt_mll_reg_twin.hip; the round-1 default, a validation twin in libdkt_diag.so since round 4): N + 1 <= 128.
 bool dkt_mll_reg_launch(const MllArgs& a, hipStream_t st);
 

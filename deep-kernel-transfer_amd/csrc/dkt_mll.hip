@@ -2,6 +2,9 @@
 // noise add, jittered Cholesky, log-det, mean cache alpha = K^-1 (y - m), and (training) the
 // gradient pieces W = d obj / d E, d logp / d(sv, mean, noise).
 //
+// DISPATCH: mll_plan() below is the ONE place that decides which kernel family serves a call (f16-split, exact-fp32 MFMA, band, tile arrays, blocked, generic in
+// LDS / in global memory) and what scratch it needs; dkt_mll_workspace_bytes_for() and dkt_mll_f32() both ask it.  A new route is registered there and nowhere else.
+//
 // GENERIC path (any N): one 256-thread workgroup per episode, classes processed in sequence
 // (the episode's W is accumulated by the same threads class after class -- no atomics, bitwise
 // reproducible).  The (N+1) x N working matrix lives in LDS when it fits (N <= ~190) and in a
@@ -19,6 +22,7 @@
 // (reference methods/DKT.py:161-163, 177, 187, 252-254, 265, 330; methods/DKT_regression.py:53-56, 92),
 // i.e. GPyTorch psd_safe_cholesky / inv_quad_logdet / cholesky_solve.
 #include "dkt_mll.h"
+#include <cstdint>
 #include <cstdlib>
 
 namespace {
@@ -214,24 +218,61 @@ void dkt_mll_generic_global_launch(MllArgs a, int b0, int count, float* ws, hipS
 // the split launch the generic kernel -- exact fp32 on the matrix itself, jitter ladder included, LDS-resident at these sizes -- redoes every unit (episode, or matrix
 // with DKT_MLL_E_PER_CLASS) whose a-priori bound 1 + sv trace(E) / noise exceeds MLL_H2_KAPPA_MAX, decided on the device: the split kernels take the trace off the
 // diagonal tiles they hold anyway and leave such a class with info = -1 (MllArgs::kappa_max; a launch of its own until ABI 7), then the generic kernel whose workgroups
-// read their flags and leave.  DKT_MLL_NO_KAPPA_GUARD = the raw split kernels (tests, A/B tools).
+// read their flags and leave (MllPlan::kappa_fixup, the H2 case of dkt_mll_f32; `mll_kappa_fixup` where the kernels' comments name it).
+// DKT_MLL_NO_KAPPA_GUARD = the raw split kernels (tests, A/B tools).
 constexpr float MLL_H2_KAPPA_MAX = 5.0e3f;
 
-static bool mll_kappa_guarded(const MllArgs& a) { return !(a.flags & DKT_MLL_NO_KAPPA_GUARD) && mll_fits_lds(a.N); }
-
-static void mll_kappa_fixup(MllArgs a, hipStream_t st) {
-    if (!mll_kappa_guarded(a)) return;
-    const int upe = (a.flags & DKT_MLL_E_PER_CLASS) ? a.C : 1;
-    const size_t units = (size_t)a.B * upe;
-    a.only_failed = a.info;                                    // the generic kernel leaves at once (one flag read per class, no barrier) unless the unit is flagged
-    a.b0 = 0; a.LD = mll_ld(a.N);
+static int mll_status() { return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH; }
+// The generic kernel on LDS-resident working matrices, one workgroup per unit (episode, or matrix with DKT_MLL_E_PER_CLASS): a route of its own and, with a.only_failed set, the fix-up pass behind the f16-split kernels.
+static int mll_generic_lds_launch(const MllArgs& a, hipStream_t st) {
+    const size_t units = (size_t)a.B * ((a.flags & DKT_MLL_E_PER_CLASS) ? a.C : 1);
     const size_t lds = (mll_vec_floats(a.N) + mll_mat_floats(a.N)) * sizeof(float);
-    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)mll_generic_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return;
+    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)mll_generic_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return DKT_ERR_LAUNCH;
     hipLaunchKernelGGL(mll_generic_kernel<false>, dim3((unsigned)units), dim3(256), lds, st, a);
+    return mll_status();
 }
 
 static int g_mll_env_read = 0, g_p2_guard = 1, g_force_f32mfma = 0;
 void dkt_mll_reload_env() { g_mll_env_read = 0; }         // dkt_reload_env()
+static void mll_read_env() {
+    if (g_mll_env_read) return;
+    const char* pg = dkt_variant_env("DKT_MLL_P2_GUARD");      // validation aid: a negative guard forces the grow-on-demand path of dkt_mll_h2.hip
+    g_p2_guard = pg ? atoi(pg) : 1;
+    const char* fm = getenv("DKT_MLL_F32MFMA");       // process-wide DKT_MLL_FORCE_F32MFMA: exact-fp32 tile products for every N <= 127 call
+    g_force_f32mfma = (fm && fm[0] == '1') ? 1 : 0;
+    g_mll_env_read = 1;
+}
+static int mll_p2_guard() { mll_read_env(); return g_p2_guard; }
+static bool mll_force_f32mfma() { mll_read_env(); return g_force_f32mfma != 0; }
+
+// THE dispatch of dkt_mll_f32, for the workspace query and the launch alike (host arithmetic only): the first route, in the order below, that applies to (B, C, N,
+// flags) and whose scratch fits in avail_bytes.  The query asks with SIZE_MAX; the launch with what the caller brought, so that a short or missing workspace falls to
+// the next route.  Per-class base matrices at 128 <= N <= 447 have the tile arrays ONLY (Tiled whatever avail_bytes: the launch answers DKT_ERR_WORKSPACE).
+// ws_bytes: what the route needs (GenericGlobal: every unit at once; the launch takes any whole number of them); kappa_fixup: the generic fix-up launch follows H2.
+enum class MllRoute { BadArg, H2, Mfma, Band, Tiled, Big, GenericLds, GenericGlobal };
+struct MllPlan { MllRoute route; size_t ws_bytes; bool kappa_fixup; };
+
+static MllPlan mll_plan(int B, int C, int N, unsigned flags, size_t avail_bytes) {
+    if (B <= 0 || C <= 0 || N <= 0) return {MllRoute::BadArg, 0, false};
+    const bool pc = (flags & DKT_MLL_E_PER_CLASS) != 0;
+    // (the register-sweep twin lives in libdkt_diag.so since round 4: dkt_diag_mll_reg_f32; per-class base matrices combine with DKT_MLL_FORCE_GENERIC / _TILED only)
+    const bool bad = (flags & DKT_MLL_FORCE_REG) || (pc && (flags & (DKT_MLL_WANT_CHOL | DKT_MLL_FORCE_F32MFMA | DKT_MLL_FORCE_BLOCKED)));
+    if (mll_force_f32mfma() && !(flags & (DKT_MLL_E_PER_CLASS | DKT_MLL_FORCE_GENERIC | DKT_MLL_FORCE_REG | DKT_MLL_FORCE_BLOCKED))) flags |= DKT_MLL_FORCE_F32MFMA;
+    const size_t gen = mll_fits_lds(N) ? 0 : (size_t)(pc ? (B < 128 ? B : 128) * C : B) * mll_mat_floats(N) * sizeof(float);
+    MllPlan p = {mll_fits_lds(N) ? MllRoute::GenericLds : MllRoute::GenericGlobal, gen, false};       // any N; LDS-resident up to N ~ 190
+    size_t ws = 0;
+    if (!(flags & DKT_MLL_FORCE_GENERIC)) {
+        if (dkt_mll_h2_serves(N, flags)) p = {MllRoute::H2, 0, !(flags & DKT_MLL_NO_KAPPA_GUARD) && mll_fits_lds(N)};
+        else if (dkt_mll_mfma_serves(N, flags)) p = {MllRoute::Mfma, 0, false};
+        else if (dkt_mll_band_applies(B, C, N, flags) && (ws = dkt_mll_band_workspace_bytes(B, C, N)) <= avail_bytes) p = {MllRoute::Band, ws, false};
+        else if (!(flags & DKT_MLL_FORCE_BLOCKED) && dkt_mll_tiled_supports(N, flags, C) && ((ws = dkt_mll_tiled_workspace_bytes_form(B, C, N, pc)) <= avail_bytes || pc))
+            p = {MllRoute::Tiled, ws, false};
+        else if (!pc && N + 1 > 128 && (ws = dkt_mll_big_workspace_bytes(B, C, N)) <= avail_bytes)
+            p = {MllRoute::Big, ws > gen ? ws : gen, false};   // (the query has always covered the generic kernel's matrices as well)
+    }
+    if (bad) p.route = MllRoute::BadArg;                        // dkt_mll_f32 refuses the flags; the query keeps answering for the shape, as it always has
+    return p;
+}
 
 extern "C" size_t dkt_mll_workspace_bytes(int B, int C, int N) {
     if (B <= 0 || N <= 0 || C <= 0) return 0;
@@ -247,18 +288,7 @@ extern "C" size_t dkt_mll_workspace_bytes(int B, int C, int N) {
 
 // What THIS call's flags need (the flag-less query reserves the larger of the shared-matrix and per-class tile layouts and the blocked path's
 // 4 N^2 floats per matrix for every call; a default shared-matrix call of a few episodes needs a tenth of that).
-extern "C" size_t dkt_mll_workspace_bytes_for(int B, int C, int N, unsigned flags) {
-    if (B <= 0 || N <= 0 || C <= 0) return 0;
-    const bool pc = (flags & DKT_MLL_E_PER_CLASS) != 0;
-    const size_t gen = mll_fits_lds(N) ? 0 : (size_t)(pc ? (B < 128 ? B : 128) * C : B) * mll_mat_floats(N) * sizeof(float);
-    if (flags & DKT_MLL_FORCE_GENERIC) return gen;
-    if (N + 1 <= 128) return (flags & DKT_MLL_WANT_CHOL) && (N + 1 + 15) / 16 > 2 ? gen : 0;      // (Cholesky output beyond N = 31: the generic kernel, LDS-resident up to N ~ 190)
-    if (dkt_mll_band_applies(B, C, N, flags)) return dkt_mll_band_workspace_bytes(B, C, N);
-    if (!(flags & DKT_MLL_FORCE_BLOCKED) && dkt_mll_tiled_supports(N, flags, C)) return dkt_mll_tiled_workspace_bytes_form(B, C, N, pc);
-    if (pc) return gen;                                                                               // N > 447 with per-class matrices: the generic kernel
-    const size_t big = dkt_mll_big_workspace_bytes(B, C, N);
-    return big > gen ? big : gen;
-}
+extern "C" size_t dkt_mll_workspace_bytes_for(int B, int C, int N, unsigned flags) { return mll_plan(B, C, N, flags, SIZE_MAX).ws_bytes; }
 
 extern "C" int dkt_mll_f32(const float* E, const float* Y, long y_bstride, const float* sv, const float* mean,
                            const float* noise, int B, int C, int N, float jitter0, int max_tries,
@@ -275,68 +305,35 @@ extern "C" int dkt_mll_f32(const float* E, const float* Y, long y_bstride, const
     a.dmean = dmean; a.dnoise = dnoise; a.jitter_used = jitter_used; a.info = info;
     a.ws = (float*)workspace; a.only_failed = nullptr; a.b0 = 0; a.B = B; a.C = C; a.N = N; a.LD = mll_ld(N);
     a.jitter0 = jitter0; a.max_tries = max_tries; a.flags = flags;
-    if (g_mll_env_read == 0) {
-        const char* pg = dkt_variant_env("DKT_MLL_P2_GUARD");      // validation aid: a negative guard forces the grow-on-demand path of dkt_mll_h2.hip
-        g_p2_guard = pg ? atoi(pg) : 1;
-        const char* fm = getenv("DKT_MLL_F32MFMA");       // process-wide DKT_MLL_FORCE_F32MFMA: exact-fp32 tile products for every N <= 127 call
-        g_force_f32mfma = (fm && fm[0] == '1') ? 1 : 0;
-        g_mll_env_read = 1;
-    }
-    a.p2_guard = g_p2_guard;
-    if (g_force_f32mfma && !(flags & (DKT_MLL_E_PER_CLASS | DKT_MLL_FORCE_GENERIC | DKT_MLL_FORCE_REG | DKT_MLL_FORCE_BLOCKED))) {
-        flags |= DKT_MLL_FORCE_F32MFMA;
-        a.flags = flags;
-    }
+    a.p2_guard = mll_p2_guard();
     hipStream_t st = (hipStream_t)stream;
-    if (flags & DKT_MLL_FORCE_REG) return DKT_ERR_BAD_ARG;     // (the register-sweep twin lives in libdkt_diag.so since round 4: dkt_diag_mll_reg_f32)
-    if (flags & DKT_MLL_E_PER_CLASS) {
-        // one base matrix per class model: the f16-split kernels with one wave per matrix (N <= 127; jitter ladder inside the kernel) or the tile-array
-        // pipeline with one W per matrix (128 <= N <= 447; failed matrices redone with the jitter ladder by the generic kernel's fix-up launch);
-        // DKT_MLL_FORCE_GENERIC (the validation twin) and N > 447: the generic kernel, one workgroup per matrix
-        if (flags & (DKT_MLL_WANT_CHOL | DKT_MLL_FORCE_REG | DKT_MLL_FORCE_F32MFMA | DKT_MLL_FORCE_BLOCKED)) return DKT_ERR_BAD_ARG;
-        if (!(flags & DKT_MLL_FORCE_GENERIC)) {
-            if (N + 1 > 128 && dkt_mll_tiled_supports(N, flags, C)) {
-                if (!workspace || workspace_bytes < dkt_mll_tiled_workspace_bytes_form(B, C, N, true)) return DKT_ERR_WORKSPACE;
-                return dkt_mll_tiled_launch(a, workspace, workspace_bytes, st);
-            }
-            if (N + 1 <= 128) {
-                a.kappa_max = mll_kappa_guarded(a) ? MLL_H2_KAPPA_MAX : 0.f;
-                if (!dkt_mll_h2_launch(a, st)) return DKT_ERR_BAD_ARG;
-                mll_kappa_fixup(a, st);
-                return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;
-            }
+    const size_t avail = workspace ? workspace_bytes : 0;
+    const MllPlan p = mll_plan(B, C, N, flags, avail);
+    switch (p.route) {
+        case MllRoute::BadArg: return DKT_ERR_BAD_ARG;
+        case MllRoute::H2:
+            a.kappa_max = p.kappa_fixup ? MLL_H2_KAPPA_MAX : 0.f;
+            dkt_mll_h2_launch(a, st);
+            if (!p.kappa_fixup) return mll_status();
+            a.only_failed = a.info;                             // the generic kernel leaves at once (one flag read per class, no barrier) unless the unit is flagged
+            return mll_generic_lds_launch(a, st);
+        case MllRoute::Mfma: dkt_mll_mfma_launch(a, st); return mll_status();
+        case MllRoute::Band: return dkt_mll_band_launch(a, workspace, workspace_bytes, st);
+        case MllRoute::Tiled:                                   // (per-class base matrices arrive here whatever the workspace: they have no other route)
+            if (avail < p.ws_bytes) return DKT_ERR_WORKSPACE;
+            return dkt_mll_tiled_launch(a, workspace, workspace_bytes, st);
+        case MllRoute::Big: return dkt_mll_big_launch(a, workspace, workspace_bytes, st);
+        case MllRoute::GenericLds: return mll_generic_lds_launch(a, st);
+        case MllRoute::GenericGlobal: {
+            // global working matrices: as many episodes per launch as the caller's workspace holds
+            const size_t per_ep = (size_t)((flags & DKT_MLL_E_PER_CLASS) ? C : 1) * mll_mat_floats(N) * sizeof(float);
+            const size_t fit = avail / per_ep;
+            if (fit < 1) return DKT_ERR_WORKSPACE;
+            const int cnt = fit < (size_t)B ? (int)fit : B;
+            for (int b0 = 0; b0 < B; b0 += cnt) dkt_mll_generic_global_launch(a, b0, (B - b0 < cnt) ? B - b0 : cnt, (float*)workspace, st);
+            return mll_status();
         }
     }
-    a.kappa_max = (N + 1 <= 128 && mll_kappa_guarded(a)) ? MLL_H2_KAPPA_MAX : 0.f;
-    if (!(flags & (DKT_MLL_FORCE_GENERIC | DKT_MLL_FORCE_REG | DKT_MLL_FORCE_F32MFMA)) && dkt_mll_h2_launch(a, st)) {
-        mll_kappa_fixup(a, st);
-        return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;
-    }
-    if (!(flags & (DKT_MLL_FORCE_GENERIC | DKT_MLL_FORCE_REG)) && dkt_mll_mfma_launch(a, st)) return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;
-    // shared base matrix, many classes, 128 <= N <= 447: one orthogonal reduction per episode (dkt_mll_band.hip); DKT_MLL_FORCE_TILED = the tile-array twin
-    if (dkt_mll_band_applies(B, C, N, flags) && workspace && workspace_bytes >= dkt_mll_band_workspace_bytes(B, C, N))
-        return dkt_mll_band_launch(a, workspace, workspace_bytes, st);
-    if (!(flags & (DKT_MLL_FORCE_GENERIC | DKT_MLL_FORCE_REG | DKT_MLL_FORCE_BLOCKED)) && dkt_mll_tiled_supports(N, flags, C) && workspace &&
-        workspace_bytes >= dkt_mll_tiled_workspace_bytes_form(B, C, N, false))
-        return dkt_mll_tiled_launch(a, workspace, workspace_bytes, st);
-    if (!(flags & (DKT_MLL_FORCE_GENERIC | DKT_MLL_E_PER_CLASS)) && N + 1 > 128 && workspace && workspace_bytes >= dkt_mll_big_workspace_bytes(B, C, N))
-        return dkt_mll_big_launch(a, workspace, workspace_bytes, st);
-    const int upe = (flags & DKT_MLL_E_PER_CLASS) ? C : 1;                 // workgroups (= working matrices) per episode
-    if (mll_fits_lds(N)) {
-        const size_t lds = (mll_vec_floats(N) + mll_mat_floats(N)) * sizeof(float);
-        if (lds > 48 * 1024) {
-            if (hipFuncSetAttribute((const void*)mll_generic_kernel<false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return DKT_ERR_LAUNCH;
-        }
-        hipLaunchKernelGGL(mll_generic_kernel<false>, dim3((unsigned)B * upe), dim3(256), lds, st, a);
-    } else {
-        // global working matrices: as many episodes per launch as the caller's workspace holds
-        const size_t per_ep = (size_t)upe * mll_mat_floats(N) * sizeof(float);
-        const size_t fit = workspace ? workspace_bytes / per_ep : 0;
-        if (fit < 1) return DKT_ERR_WORKSPACE;
-        const int cnt = fit < (size_t)B ? (int)fit : B;
-        for (int b0 = 0; b0 < B; b0 += cnt) dkt_mll_generic_global_launch(a, b0, (B - b0 < cnt) ? B - b0 : cnt, (float*)workspace, st);
-    }
-    return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;
+    return DKT_ERR_BAD_ARG;                                     // (unreachable: every route returns)
 }
+

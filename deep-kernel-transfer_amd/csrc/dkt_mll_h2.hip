@@ -1320,19 +1320,19 @@ void launch_h2(const MllArgs& a, hipStream_t st) {
 
 void dkt_mll_h2_reload_env() { g_h2e_minb = -1; }        // dkt_reload_env(): tests / A-B tools flip DKT_MLL_H2E_MINB inside one process
 
-// N + 1 <= 128 and no Cholesky output requested; false otherwise (the caller falls through to dkt_mll_mfma_launch).
-bool dkt_mll_h2_launch(const MllArgs& a, hipStream_t st) {
-    if (a.flags & DKT_MLL_WANT_CHOL) return false;
-    const int nt = (a.N + 1 + 15) / 16;
-    switch (nt) {
-        case 1: launch_h2<1>(a, st); return true;
-        case 2: launch_h2<2>(a, st); return true;
-        case 3: launch_h2<3>(a, st); return true;
-        case 4: launch_h2<4>(a, st); return true;
-        case 5: launch_h2<5>(a, st); return true;
-        case 6: launch_h2<6>(a, st); return true;
-        case 7: launch_h2<7>(a, st); return true;
-        case 8: launch_h2<8>(a, st); return true;
-        default: return false;
+// The calls these kernels serve: N + 1 <= 128 (8 tiles), no Cholesky output, no exact-fp32 request.
+bool dkt_mll_h2_serves(int N, unsigned flags) { return N + 1 <= 128 && !(flags & (DKT_MLL_WANT_CHOL | DKT_MLL_FORCE_F32MFMA)); }
+
+void dkt_mll_h2_launch(const MllArgs& a, hipStream_t st) {
+    switch ((a.N + 1 + 15) / 16) {
+        case 1: launch_h2<1>(a, st); break;
+        case 2: launch_h2<2>(a, st); break;
+        case 3: launch_h2<3>(a, st); break;
+        case 4: launch_h2<4>(a, st); break;
+        case 5: launch_h2<5>(a, st); break;
+        case 6: launch_h2<6>(a, st); break;
+        case 7: launch_h2<7>(a, st); break;
+        case 8: launch_h2<8>(a, st); break;
+        default: break;                                    // unreachable: mll_plan() sends only what dkt_mll_h2_serves()
     }
 }

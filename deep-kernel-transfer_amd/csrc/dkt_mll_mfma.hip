@@ -679,23 +679,25 @@ void launch_mfma(const MllArgs& a, hipStream_t st) {
 
 // The product library serves DKT_MLL_WANT_CHOL here for N + 1 <= 32 (the regression head's conditioning sets, DKT_regression.py:84-93: 5 .. 19 rows; larger
 // requests take the generic kernel) and nothing else; the twins library (-DDKT_TWINS) has every size with and without the Cholesky output -- the exact-fp32
-// twin of the f16-split kernels.  Returns false when the call is not served.
-bool dkt_mll_mfma_launch(const MllArgs& a, hipStream_t st) {
-    const int nt = (a.N + 1 + 15) / 16;
+// twin of the f16-split kernels.  This predicate is the one place that knows the difference (the switch below only instantiates what it admits).
+bool dkt_mll_mfma_serves(int N, unsigned flags) {
 #ifndef DKT_TWINS
-    if (!(a.flags & DKT_MLL_WANT_CHOL) || nt > 2) return false;
+    if (!(flags & DKT_MLL_WANT_CHOL) || N + 1 > 32) return false;
 #endif
-    switch (nt) {
-        case 1: launch_mfma<1>(a, st); return true;
-        case 2: launch_mfma<2>(a, st); return true;
+    return N + 1 <= 128;
+}
+void dkt_mll_mfma_launch(const MllArgs& a, hipStream_t st) {
+    switch ((a.N + 1 + 15) / 16) {
+        case 1: launch_mfma<1>(a, st); break;
+        case 2: launch_mfma<2>(a, st); break;
 #ifdef DKT_TWINS
-        case 3: launch_mfma<3>(a, st); return true;
-        case 4: launch_mfma<4>(a, st); return true;
-        case 5: launch_mfma<5>(a, st); return true;
-        case 6: launch_mfma<6>(a, st); return true;
-        case 7: launch_mfma<7>(a, st); return true;
-        case 8: launch_mfma<8>(a, st); return true;
+        case 3: launch_mfma<3>(a, st); break;
+        case 4: launch_mfma<4>(a, st); break;
+        case 5: launch_mfma<5>(a, st); break;
+        case 6: launch_mfma<6>(a, st); break;
+        case 7: launch_mfma<7>(a, st); break;
+        case 8: launch_mfma<8>(a, st); break;
 #endif
-        default: return false;
+        default: break;                                    // unreachable: mll_plan() sends only what dkt_mll_mfma_serves()
     }
 }

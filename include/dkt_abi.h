@@ -118,7 +118,12 @@ int dkt_gram_f32(const float* A, const float* Bm, float* E, int B, int M, int N,
  */
 size_t dkt_mll_workspace_bytes(int B, int C, int N);
 /* The same for ONE call: the bytes dkt_mll_f32 needs with exactly these flags (never more than dkt_mll_workspace_bytes(B, C, N), which covers every
- * flag combination; a default shared-matrix call of a few 420-row episodes needs a tenth of it).  (ABI 4) */
+ * flag combination; a default shared-matrix call of a few 420-row episodes needs a tenth of it).  (ABI 4)
+ * Query and launch share one plan: the call is served by the first route, in this order, that applies to (B, C, N, flags) -- after the process-wide
+ * DKT_MLL_F32MFMA=1 has added DKT_MLL_FORCE_F32MFMA to them -- and whose scratch the workspace holds:  N <= 127: f16-split kernels | exact-fp32 MFMA kernel |
+ * generic kernel, none needs scratch;  N >= 128: band reduction -> tile arrays -> blocked path -> generic kernel (no scratch up to N ~ 190, above any whole number
+ * of working matrices).  The query names the first of them; a call that brings less (or NULL) is served by the next that fits, DKT_ERR_WORKSPACE only when none
+ * does.  Per-class base matrices (DKT_MLL_E_PER_CLASS) at 128 <= N <= 447 have the tile arrays alone: DKT_ERR_WORKSPACE below what the query names. */
 size_t dkt_mll_workspace_bytes_for(int B, int C, int N, unsigned flags);
 
 /*
