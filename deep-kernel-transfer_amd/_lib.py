@@ -16,7 +16,7 @@ Seven in-tree shared objects, all hipcc --offload-arch=gfx950:
                           environment switches of DESIGN.md's appendix.  Same ABI.  Tests and A/B tools only (DKT_TWINS=1 + a variant switch);
   diag   libdkt_diag.so   measurement-only kernels (stream ceilings, co-residency spinners, the round-1 register-sweep kernel): no header, no version.
 
-An object file's cache key hashes its source, every csrc/*.h and csrc/*.inc, include/dkt_abi.h and the ABI header of its own library -- what the sources
+An object file's cache key hashes its source, every csrc/*.h, csrc/*.inc and csrc/*.def, include/dkt_abi.h and the ABI header of its own library -- what the sources
 include -- so an edit to one library's header recompiles that library only.
 
 Adding a library: one ABI header under include/, one signature dict, one `LibSpec` entry in `LIBS` (+ the one-line `load_*` / `build_*` names its callers want).
@@ -47,6 +47,7 @@ SIGNATURES = {
     "dkt_abi_version": (_c_i, []),
     "dkt_device_cu_count": (_c_i, []),
     "dkt_reload_env": (None, []),
+    "dkt_env_value": (ctypes.c_char_p, [ctypes.c_char_p]),
     "dkt_gram_f32": (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p]),
     "dkt_mll_workspace_bytes": (ctypes.c_size_t, [_c_i, _c_i, _c_i]),
     "dkt_mll_workspace_bytes_for": (ctypes.c_size_t, [_c_i, _c_i, _c_i, ctypes.c_uint]),
@@ -100,6 +101,7 @@ X_F16 = 2
 X16_SIGNATURES = {
     "dkt_x16_abi_version": (_c_i, []),
     "dkt_x16_reload_env": (None, []),
+    "dkt_x16_env_value": (ctypes.c_char_p, [ctypes.c_char_p]),
     "dkt_bn_stats_x16": (_c_i, [_c_p, _c_i, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p]),
     "dkt_gram_bn_x16": (_c_i, [_c_p, _c_i, _c_p, _c_p, ctypes.c_long, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p]),
     "dkt_gram_bn_train_x16": (_c_i, [_c_p, _c_i, _c_p, _c_p, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p]),
@@ -248,10 +250,10 @@ def _read(path: str) -> bytes:
 
 
 def _digest(src: str, spec: LibSpec) -> str:
-    """Content hash of a source, the headers it can include (every csrc/*.h and *.inc, include/dkt_abi.h, its library's own ABI header) and the flags: the
+    """Content hash of a source, the headers it can include (every csrc/*.h, *.inc and *.def, include/dkt_abi.h, its library's own ABI header) and the flags: the
     object cache key (mtimes do not survive a checkout)."""
     import hashlib
-    headers = (sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) +
+    headers = (sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc", ".def"))) +
                [os.path.join(INCLUDE, f) for f in sorted({"dkt_abi.h", spec.header} - {None})])
     h = hashlib.sha256()
     for f in [src] + headers:

@@ -345,20 +345,16 @@ extern "C" int dkt_class_kernel_f32(const float* base, int kind, const float* pa
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((NN + 255) / 256, B), block(256);
     switch (kind) {
-        case DKT_CLASSMAP_RBF: hipLaunchKernelGGL(class_kernel_fwd<DKT_CLASSMAP_RBF>, grid, block, dkt_lds_pad("DKT_PAD_CK_FWD"), st, base, param, power, E, C, NN); break;
-        case DKT_CLASSMAP_MATERN25: hipLaunchKernelGGL(class_kernel_fwd<DKT_CLASSMAP_MATERN25>, grid, block, dkt_lds_pad("DKT_PAD_CK_FWD"), st, base, param, power, E, C, NN); break;
-        case DKT_CLASSMAP_POLY: hipLaunchKernelGGL(class_kernel_fwd<DKT_CLASSMAP_POLY>, grid, block, dkt_lds_pad("DKT_PAD_CK_FWD"), st, base, param, power, E, C, NN); break;
+        case DKT_CLASSMAP_RBF: hipLaunchKernelGGL(class_kernel_fwd<DKT_CLASSMAP_RBF>, grid, block, dkt_lds_pad(DKT_SW_PAD_CK_FWD), st, base, param, power, E, C, NN); break;
+        case DKT_CLASSMAP_MATERN25: hipLaunchKernelGGL(class_kernel_fwd<DKT_CLASSMAP_MATERN25>, grid, block, dkt_lds_pad(DKT_SW_PAD_CK_FWD), st, base, param, power, E, C, NN); break;
+        case DKT_CLASSMAP_POLY: hipLaunchKernelGGL(class_kernel_fwd<DKT_CLASSMAP_POLY>, grid, block, dkt_lds_pad(DKT_SW_PAD_CK_FWD), st, base, param, power, E, C, NN); break;
         default: return DKT_ERR_BAD_ARG;
     }
     return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;
 }
 
-static int g_ck_v4 = -1, g_ck_n128 = -1;
-void dkt_classkernel_reload_env() { g_ck_v4 = -1; g_ck_n128 = -1; }     // dkt_reload_env()
-static bool class_bwd_n128() {                                         // DKT_CLASS_BWD_N128=0 (twins library): the dword kernel for N <= 128 too (A/B, twin test)
-    if (g_ck_n128 < 0) { const char* v = dkt_variant_env("DKT_CLASS_BWD_N128"); g_ck_n128 = (v && v[0] == '0') ? 0 : 1; }
-    return g_ck_n128 != 0;
-}
+static bool class_bwd_n128() { return dkt_env_on(DKT_SW_CLASS_BWD_N128); }      // DKT_CLASS_BWD_N128=0 (twins library): the dword kernel for N <= 128 too (A/B, twin test)
+static bool class_bwd_v4() { return dkt_env_on(DKT_SW_CLASS_BWD_V4); }          // DKT_CLASS_BWD_V4=0: the dword kernel, a measurement twin
 
 extern "C" int dkt_class_kernel_bwd_nsplit(int B, int N) {
     if (B <= 0 || N <= 0) return 1;
@@ -375,25 +371,24 @@ extern "C" int dkt_class_kernel_bwd_f32(const float* W, const float* base, int k
     if (C > 32) return DKT_ERR_TOO_LARGE;                                // 32 x 512 floats of LDS partials (64 KB)
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(B * nsplit), block(CKB_T);
-    if (g_ck_v4 < 0) { const char* v = dkt_variant_env("DKT_CLASS_BWD_V4"); g_ck_v4 = (v && v[0] == '0') ? 0 : 1; }      // (0: the dword kernel, a measurement twin)
     // round 5: all loads of a row in flight, constants and partials in registers.  Same-box A/B (tools/class_bwd_ab.py, profiles/r05/v12_class_bwd_ab.log; 2048 episodes,
     // C = 5): N = 105 rbf 0.294 -> 0.139 ms (0.27 -> 0.57 of HBM), matern 0.351 -> 0.214, poly 0.241 -> 0.132, N = 80 0.204 -> 0.096; C = 8, N = 128: 0.213 -> 0.145;
     // N = 25 (a row fills 25 of a wave's 128 column slots) 0.092 -> 0.128: from 65 rows.
     if (N > 64 && N <= 128 && C <= 8 && class_bwd_n128()) {
         switch (kind) {
-            case DKT_CLASSMAP_RBF: hipLaunchKernelGGL(class_kernel_bwd_n128<DKT_CLASSMAP_RBF>, grid, block, dkt_lds_pad("DKT_PAD_CK_BWD"), st, W, base, param, power, Wp, dparam, C, N, nsplit); break;
-            case DKT_CLASSMAP_MATERN25: hipLaunchKernelGGL(class_kernel_bwd_n128<DKT_CLASSMAP_MATERN25>, grid, block, dkt_lds_pad("DKT_PAD_CK_BWD"), st, W, base, param, power, Wp, dparam, C, N, nsplit); break;
-            case DKT_CLASSMAP_POLY: hipLaunchKernelGGL(class_kernel_bwd_n128<DKT_CLASSMAP_POLY>, grid, block, dkt_lds_pad("DKT_PAD_CK_BWD"), st, W, base, param, power, Wp, dparam, C, N, nsplit); break;
+            case DKT_CLASSMAP_RBF: hipLaunchKernelGGL(class_kernel_bwd_n128<DKT_CLASSMAP_RBF>, grid, block, dkt_lds_pad(DKT_SW_PAD_CK_BWD), st, W, base, param, power, Wp, dparam, C, N, nsplit); break;
+            case DKT_CLASSMAP_MATERN25: hipLaunchKernelGGL(class_kernel_bwd_n128<DKT_CLASSMAP_MATERN25>, grid, block, dkt_lds_pad(DKT_SW_PAD_CK_BWD), st, W, base, param, power, Wp, dparam, C, N, nsplit); break;
+            case DKT_CLASSMAP_POLY: hipLaunchKernelGGL(class_kernel_bwd_n128<DKT_CLASSMAP_POLY>, grid, block, dkt_lds_pad(DKT_SW_PAD_CK_BWD), st, W, base, param, power, Wp, dparam, C, N, nsplit); break;
             default: return DKT_ERR_BAD_ARG;
         }
         return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;
     }
     // (N <= 128: a row of 4-column groups leaves more than half of a wave's lanes idle -- 0.58 vs 0.28 ms at N = 105, C = 5, 2048 episodes: the dword kernel stays for C > 8)
-    if (N > 128 && N <= 512 && g_ck_v4 != 0) {
+    if (N > 128 && N <= 512 && class_bwd_v4()) {
         switch (kind) {
-            case DKT_CLASSMAP_RBF: hipLaunchKernelGGL(class_kernel_bwd_v4<DKT_CLASSMAP_RBF>, grid, block, dkt_lds_pad("DKT_PAD_CK_BWD"), st, W, base, param, power, Wp, dparam, C, N, nsplit); break;
-            case DKT_CLASSMAP_MATERN25: hipLaunchKernelGGL(class_kernel_bwd_v4<DKT_CLASSMAP_MATERN25>, grid, block, dkt_lds_pad("DKT_PAD_CK_BWD"), st, W, base, param, power, Wp, dparam, C, N, nsplit); break;
-            case DKT_CLASSMAP_POLY: hipLaunchKernelGGL(class_kernel_bwd_v4<DKT_CLASSMAP_POLY>, grid, block, dkt_lds_pad("DKT_PAD_CK_BWD"), st, W, base, param, power, Wp, dparam, C, N, nsplit); break;
+            case DKT_CLASSMAP_RBF: hipLaunchKernelGGL(class_kernel_bwd_v4<DKT_CLASSMAP_RBF>, grid, block, dkt_lds_pad(DKT_SW_PAD_CK_BWD), st, W, base, param, power, Wp, dparam, C, N, nsplit); break;
+            case DKT_CLASSMAP_MATERN25: hipLaunchKernelGGL(class_kernel_bwd_v4<DKT_CLASSMAP_MATERN25>, grid, block, dkt_lds_pad(DKT_SW_PAD_CK_BWD), st, W, base, param, power, Wp, dparam, C, N, nsplit); break;
+            case DKT_CLASSMAP_POLY: hipLaunchKernelGGL(class_kernel_bwd_v4<DKT_CLASSMAP_POLY>, grid, block, dkt_lds_pad(DKT_SW_PAD_CK_BWD), st, W, base, param, power, Wp, dparam, C, N, nsplit); break;
             default: return DKT_ERR_BAD_ARG;
         }
         return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;

@@ -10,16 +10,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Measurement / validation switches.  The PRODUCT library (libdkt_hip.so) has none of them: every variant kernel and every switch
 // that selects one is compiled out, the defaults are the product.  The twins library (libdkt_twins.so: the same sources with -DDKT_TWINS, loaded by the
-// tests and the A/B tools only) reads them from the environment.
-#include <cstdlib>
-static inline const char* dkt_variant_env(const char* name) {
-#ifdef DKT_TWINS
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
+// tests and the A/B tools only) reads them from the environment: dkt_env.h, over the table dkt_switches.def.
+#include "dkt_env.h"
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -60,7 +52,4 @@ __device__ __forceinline__ float4 load4_guard(const float* row, int col, int nco
 
 // Twins library only: bytes of dynamic LDS a launch reserves without touching them -- caps the workgroups per CU for occupancy A/Bs of the streaming kernels
 // (tools/occupancy_pad_ab.py; the product returns 0).
-static inline unsigned dkt_lds_pad(const char* name) {
-    const char* v = dkt_variant_env(name);
-    return v ? (unsigned)atoi(v) : 0u;
-}
+static inline unsigned dkt_lds_pad(DktSwitch pad) { return (unsigned)dkt_env_int(pad, 0); }

@@ -20,13 +20,9 @@
 
 // Episode-resident squared-distance / RBF build of dkt_gram_f32 (symmetric, 32 < N <= 128, D % 4 == 0, 16-byte aligned Z, a batch that
 // fills the GPU); returns false when it does not apply (the generic 64 x 64-tile kernel then runs).
-static int g_dist_ep_minb = -1, g_dist_ep_on = -1;           // DKT_GRAM_EP_MINB / DKT_GRAM_DIST_EP, read at the first call and at dkt_reload_env()
-void dkt_frontend_reload_env() { g_dist_ep_minb = -1; g_dist_ep_on = -1; g_bn_f16 = -1; g_stage_synced = 0; }
 bool dkt_gram_dist_ep_launch(const float* Z, float* E, int B, int N, int D, int kind, const float* lengthscale, hipStream_t st) {
-    if (g_dist_ep_minb < 0) { const char* v = getenv("DKT_GRAM_EP_MINB"); g_dist_ep_minb = v ? atoi(v) : 64; }
-    if (g_dist_ep_on < 0) { const char* v = dkt_variant_env("DKT_GRAM_DIST_EP"); g_dist_ep_on = (v && v[0] == '0') ? 0 : 1; }
-    const int minb = g_dist_ep_minb;
-    const bool on = g_dist_ep_on != 0;
+    const int minb = dkt_env_int(DKT_SW_GRAM_EP_MINB, 64);          // (64 here, 32 for the linear kernels of dkt_gram_ep.hip)
+    const bool on = dkt_env_on(DKT_SW_GRAM_DIST_EP);
     if (!on || N <= 32 || N > 128 || (D & 3) || ((uintptr_t)Z & 15) || B < minb || !lengthscale) return false;
     if (kind != DKT_KERNEL_RBF && kind != DKT_KERNEL_SQDIST) return false;
     BnTrainOut bo{};

@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void normalize_bn_bwd_cols_kernel(const float*
 // the launches behind dkt_affine_normalize_* / dkt_normalize_bn_bwd_* (the host checks are the callers')
 template <typename XT>
 int affine_normalize_launch(const XT* X, const float* a, const float* s, long ab_bstride, float* Zn, float* rnorm, long rows, int N, int D, hipStream_t st) {
-    hipLaunchKernelGGL(affine_normalize_kernel<XT>, dim3((unsigned)((rows + 3) / 4)), dim3(256), dkt_lds_pad("DKT_PAD_AFFNORM"), st, X, a, s, ab_bstride, Zn, rnorm, rows, N, D);
+    hipLaunchKernelGGL(affine_normalize_kernel<XT>, dim3((unsigned)((rows + 3) / 4)), dim3(256), dkt_lds_pad(DKT_SW_PAD_AFFNORM), st, X, a, s, ab_bstride, Zn, rnorm, rows, N, D);
     return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;
 }
 
@@ -196,7 +196,7 @@ int normalize_bn_bwd_launch(const float* dZn, const float* Zn, const XT* X, cons
                             XT* dX, float* dgamma_part, float* dbeta_part, float* rowdot_ws, int B, int N, int D, bool train, hipStream_t st) {
     const long rows = (long)B * N;
     const int nslab = (D + 31) / 32;
-    hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), dkt_lds_pad("DKT_PAD_ROWDOT"), st, Zn, dZn, rowdot_ws, rows, D);
+    hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), dkt_lds_pad(DKT_SW_PAD_ROWDOT), st, Zn, dZn, rowdot_ws, rows, D);
     if (train) {
         const size_t lds = ((size_t)N * 32 + 32 * 8 * 8) * sizeof(float);
         if (lds > 48 * 1024 &&
@@ -205,7 +205,7 @@ int normalize_bn_bwd_launch(const float* dZn, const float* Zn, const XT* X, cons
         hipLaunchKernelGGL((normalize_bn_bwd_cols_kernel<XT, true>), dim3((unsigned)(B * nslab)), dim3(256), lds, st, dZn, Zn, X, a, a_bstride, mean, rstd, rnorm, rowdot_ws, dX,
                            dgamma_part, dbeta_part, N, D, nslab);
     } else {
-        hipLaunchKernelGGL((normalize_bn_bwd_cols_kernel<XT, false>), dim3((unsigned)(B * nslab)), dim3(256), dkt_lds_pad("DKT_PAD_NBB"), st, dZn, Zn, X, a, a_bstride, mean, rstd, rnorm, rowdot_ws, dX,
+        hipLaunchKernelGGL((normalize_bn_bwd_cols_kernel<XT, false>), dim3((unsigned)(B * nslab)), dim3(256), dkt_lds_pad(DKT_SW_PAD_NBB), st, dZn, Zn, X, a, a_bstride, mean, rstd, rnorm, rowdot_ws, dX,
                            dgamma_part, dbeta_part, N, D, nslab);
     }
     return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;

@@ -993,16 +993,11 @@ __global__ __launch_bounds__(64 * NT, DKT_FE_BWD_WPE) void gram_bn_bwd_ep_kernel
 #undef FCLK
 }
 
-static int g_stage_synced = 0;                          // twins library: DKT_LDS_STAGE_OLD reaches the device at the first launch and after dkt_reload_env()
-void lds_stage_env_sync_once() {
-    if (!g_stage_synced) { lds_stage_env_sync(); g_stage_synced = 1; }
-}
-
 template <typename XT, int NT>
 void launch_gram_bn_bwd(const float* W, const float* E, const XT* X, const float* a, const float* s, long abs, const float* mean,
                         const float* rstd, const float* rnorm, const float* sc, XT* dX, float* dg, float* db, int B, int N, int D,
                         bool train_bn, hipStream_t st) {
-    lds_stage_env_sync_once();
+    lds_stage_env_sync();                     // (twins library: DKT_LDS_STAGE_OLD reaches the device at the first launch and after dkt_reload_env())
     if (train_bn) hipLaunchKernelGGL((gram_bn_bwd_ep_kernel<XT, NT, true>), dim3(B), dim3(64 * NT), 0, st, W, E, X, a, s, abs, mean, rstd, rnorm, sc, dX, dg, db, N, D);
     else hipLaunchKernelGGL((gram_bn_bwd_ep_kernel<XT, NT, false>), dim3(B), dim3(64 * NT), 0, st, W, E, X, a, s, abs, mean, rstd, rnorm, sc, dX, dg, db, N, D);
 }
@@ -1025,11 +1020,7 @@ int gram_bn_bwd_dispatch(const float* W, const float* E, const XT* X, const floa
 }
 
 // DKT_GRAM_BN_F16 (twins library only; default 1): 0 = the 3-way bf16 split in the train-mode fused forward at every N (the round-3 kernel: A/B, twin test)
-static int g_bn_f16 = -1;
-bool bn_train_f16() {
-    if (g_bn_f16 < 0) { const char* v = dkt_variant_env("DKT_GRAM_BN_F16"); g_bn_f16 = (v && v[0] == '0') ? 0 : 1; }
-    return g_bn_f16 != 0;
-}
+bool bn_train_f16() { return dkt_env_on(DKT_SW_GRAM_BN_F16); }
 
 template <typename XT, int NT>
 void launch_gram_bn(const XT* X, const float* A, const float* S, long abs, float* E, float* rnorm, int B, int N, int D, hipStream_t st,
@@ -1042,12 +1033,12 @@ void launch_gram_bn(const XT* X, const float* A, const float* S, long abs, float
     } else if (bo) {
         if constexpr (NT >= 3) {
             if (bn_train_f16()) {                        // f16 split under the a-priori bound, then the fix-up pass over the episodes it flagged
-                hipLaunchKernelGGL((gram_bn_train_f16_kernel<XT, NT>), dim3(B), dim3(256), dkt_lds_pad("DKT_PAD_FE_FWD"), st, X, A, S, E, rnorm, N, D, *bo);
-                hipLaunchKernelGGL((gram_bn_sym_ep_kernel<XT, NT, true>), dim3(B), dim3(256), dkt_lds_pad("DKT_PAD_FE_FWD"), st, X, A, S, 0L, E, rnorm, N, D, *bo, 1);
+                hipLaunchKernelGGL((gram_bn_train_f16_kernel<XT, NT>), dim3(B), dim3(256), dkt_lds_pad(DKT_SW_PAD_FE_FWD), st, X, A, S, E, rnorm, N, D, *bo);
+                hipLaunchKernelGGL((gram_bn_sym_ep_kernel<XT, NT, true>), dim3(B), dim3(256), dkt_lds_pad(DKT_SW_PAD_FE_FWD), st, X, A, S, 0L, E, rnorm, N, D, *bo, 1);
                 return;
             }
         }
-        hipLaunchKernelGGL((gram_bn_sym_ep_kernel<XT, NT, true>), dim3(B), dim3(256), dkt_lds_pad("DKT_PAD_FE_FWD"), st, X, A, S, 0L, E, rnorm, N, D, *bo, 0);
+        hipLaunchKernelGGL((gram_bn_sym_ep_kernel<XT, NT, true>), dim3(B), dim3(256), dkt_lds_pad(DKT_SW_PAD_FE_FWD), st, X, A, S, 0L, E, rnorm, N, D, *bo, 0);
     } else hipLaunchKernelGGL((gram_bn_sym_ep_kernel<XT, NT, false>), dim3(B), dim3(256), 0, st, X, A, S, abs, E, rnorm, N, D, BnTrainOut{}, 0);
 }
 

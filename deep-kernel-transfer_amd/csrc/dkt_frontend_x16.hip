@@ -21,7 +21,8 @@ bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" int dkt_x16_abi_version(void) { return DKT_X16_ABI_VERSION; }
 
-extern "C" void dkt_x16_reload_env(void) { g_bn_f16 = -1; g_stage_synced = 0; }
+extern "C" void dkt_x16_reload_env(void) { dkt_env_reload(); }
+extern "C" const char* dkt_x16_env_value(const char* name) { return dkt_env_by_name(name); }
 
 extern "C" int dkt_bn_stats_x16(const void* X, int xdtype, const float* gamma, const float* beta, float eps, float* mean, float* rstd,
                                 float* a, float* s, float* var_unbiased, int B, int N, int D, void* stream) {

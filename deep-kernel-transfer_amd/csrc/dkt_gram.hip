@@ -427,8 +427,7 @@ extern "C" int dkt_gram_f32(const float* A, const float* Bm, float* E, int B, in
     const bool sym = (Bm == nullptr);
     if (sym && M != N) return DKT_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const char* sm = dkt_variant_env("DKT_GRAM_SMALL");
-    const bool small_ok = !(sm && sm[0] == '0');
+    const bool small_ok = dkt_env_on(DKT_SW_GRAM_SMALL);
     if (sym && small_ok && dkt_gram_small_launch(A, E, B, N, D, kind, lengthscale, st))
         return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;
     if (sym && kind != DKT_KERNEL_LINEAR && dkt_gram_dist_ep_launch(A, E, B, N, D, kind, lengthscale, st))
@@ -461,11 +460,8 @@ extern "C" int dkt_gram_f32(const float* A, const float* Bm, float* E, int B, in
 extern "C" int dkt_gram_bwd_f32(const float* W, const float* Z, float* dZ, int B, int N, int D,
                                 const float* ep_scale, unsigned flags, void* stream) {
     if (!W || !Z || !dZ || B <= 0 || N <= 0 || D <= 0 || (flags & ~(DKT_GRAM_UNIT_ROWS | DKT_GRAM_W_SYMMETRIC))) return DKT_ERR_BAD_ARG;
-    {
-        const char* sm = dkt_variant_env("DKT_GRAM_SMALL");
-        if (!(sm && sm[0] == '0') && dkt_gram_small_bwd_launch(W, Z, dZ, B, N, D, ep_scale, (hipStream_t)stream))
-            return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;
-    }
+    if (dkt_env_on(DKT_SW_GRAM_SMALL) && dkt_gram_small_bwd_launch(W, Z, dZ, B, N, D, ep_scale, (hipStream_t)stream))
+        return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;
     if (dkt_gram_bwd_ep_launch(W, Z, dZ, B, N, D, ep_scale, (flags & DKT_GRAM_UNIT_ROWS) != 0, (hipStream_t)stream))
         return hipGetLastError() == hipSuccess ? DKT_OK : DKT_ERR_LAUNCH;
     if (dkt_gram_bwd_big_launch(W, Z, dZ, B, N, D, ep_scale, flags, (hipStream_t)stream))

@@ -489,11 +489,7 @@ __global__ __launch_bounds__(512, 1) void gram_sym_bigep_f16x2_kernel(const floa
     }
 }
 
-static int g_bwd_rows8 = -1;
-static bool gram_bwd_rows8_enabled() {
-    if (g_bwd_rows8 < 0) { const char* v = dkt_variant_env("DKT_GRAM_BWD_ROWS8"); g_bwd_rows8 = (v && v[0] == '0') ? 0 : 1; }
-    return g_bwd_rows8 != 0;
-}
+static bool gram_bwd_rows8_enabled() { return dkt_env_on(DKT_SW_GRAM_BWD_ROWS8); }
 
 template <int KS>
 void launch_rows(const float* W, const float* Z, float* dZ, int B, int N, int D, const float* sc, hipStream_t st) {
@@ -508,24 +504,19 @@ void launch_rows(const float* W, const float* Z, float* dZ, int B, int N, int D,
     if (!kRows4 || (gram_bwd_rows8_enabled() && (KS >= 10 || (D >= 128 && (long)B * ((N + 127) / 128) >= 256)))) {
         const int nrb = (N + 127) / 128;
         const int grid = 8 * ((B + 7) / 8) * nrb;
-        hipLaunchKernelGGL((gram_bwd_rows_f16x2_kernel<KS, 8>), dim3(grid), dim3(512), dkt_lds_pad("DKT_PAD_GRAM_BIG_BWD"), st, W, Z, dZ, B, N, D, sc, nrb);
+        hipLaunchKernelGGL((gram_bwd_rows_f16x2_kernel<KS, 8>), dim3(grid), dim3(512), dkt_lds_pad(DKT_SW_PAD_GRAM_BIG_BWD), st, W, Z, dZ, B, N, D, sc, nrb);
         return;
     }
     if constexpr (kRows4) {
         const int nrb = (N + 63) / 64;
         const int grid = 8 * ((B + 7) / 8) * nrb;
-        hipLaunchKernelGGL((gram_bwd_rows_f16x2_kernel<KS, 4>), dim3(grid), dim3(256), dkt_lds_pad("DKT_PAD_GRAM_BIG_BWD"), st, W, Z, dZ, B, N, D, sc, nrb);
+        hipLaunchKernelGGL((gram_bwd_rows_f16x2_kernel<KS, 4>), dim3(grid), dim3(256), dkt_lds_pad(DKT_SW_PAD_GRAM_BIG_BWD), st, W, Z, dZ, B, N, D, sc, nrb);
     }
 }
 
 }  // namespace
 
-static int g_big_ep = -1;
-static bool gram_big_ep_enabled() {
-    if (g_big_ep < 0) { const char* v = dkt_variant_env("DKT_GRAM_BIG_EP"); g_big_ep = (v && v[0] == '0') ? 0 : 1; }
-    return g_big_ep != 0;
-}
-void dkt_gram_big_reload_env();                          // dkt_reload_env(); defined below the switches
+static bool gram_big_ep_enabled() { return dkt_env_on(DKT_SW_GRAM_BIG_EP); }
 
 // Returns true when the kernel was launched (128 < N <= 448, unit rows, symmetric W, D % 4 == 0, 16-byte aligned Z / dZ).
 bool dkt_gram_bwd_big_launch(const float* W, const float* Z, float* dZ, int B, int N, int D, const float* sc, unsigned flags, hipStream_t st) {
@@ -539,8 +530,6 @@ bool dkt_gram_bwd_big_launch(const float* W, const float* Z, float* dZ, int B, i
     else launch_rows<14>(W, Z, dZ, B, N, D, sc, st);
     return true;
 }
-
-void dkt_gram_big_reload_env() { g_big_ep = -1; g_bwd_rows8 = -1; }
 
 // Returns true when the kernel was launched (symmetric linear Gram, N > 128, D % 4 == 0, 16-byte aligned Z).
 bool dkt_gram_sym_big_launch(const float* Z, float* E, int B, int N, int D, bool unit, hipStream_t st) {

@@ -771,41 +771,19 @@ __global__ __launch_bounds__(64 * NT, (2 * NT + 3) / 4) void gram_bwd_ep_f16x2_k
     }
 }
 
-// Measurement / validation switches: read from the environment ONCE, at the first launch -- not per call.
-// dkt_reload_env() (below, exported for the test-suite and the A/B tools, which flip switches inside one process) re-reads them.
-struct GramEnv {
-    int ep, fewep, minb, split, ep_bk, ep_bd, unit_var, split_var, bwd_unit_var, bwd_split_var, bwd_unit_mind, bwd_split_mind;
-    static int get(const char* name, int dflt) {                 // variant switch: twins library only
-        const char* v = dkt_variant_env(name);
-        return v ? atoi(v) : dflt;
-    }
-    static int get_product(const char* name, int dflt) {         // dispatch threshold: product library too
-        const char* v = getenv(name);
-        return v ? atoi(v) : dflt;
-    }
-    void load() {
-        ep = get("DKT_GRAM_EP", 1); fewep = get("DKT_GRAM_FEWEP", 1); minb = get_product("DKT_GRAM_EP_MINB", 32); split = get("DKT_GRAM_SPLIT", 1);
-        ep_bk = get("DKT_GRAM_EP_BK", 64); ep_bd = get("DKT_GRAM_EP_BD", 32);
-        // Round 4 (tools/sweep_ep_variants.py + the in-step A/B of tools/r4_run12.sh, profiles/r04/v14_ep_variant_sweep.log): the forward with non-temporal Z loads
-        // (22232: -1 % at D = 1600, -5 % at D = 512, -4 % at D = 64 against 2223) and, below D = 1024, the backward with ONE LDS image and prefetch depth 1
-        // (211: 0.20 vs 0.24 ms at cfg1, 0.57 vs 0.68 ms at cfg3; equal at D = 1600, where 1222 -- two images, non-temporal dZ stores -- stays): 0 = this choice by D.
-        unit_var = get("DKT_GRAM_UNIT_VAR", 22232); split_var = get("DKT_GRAM_SPLIT_VAR", 11);
-        bwd_unit_var = get("DKT_GRAM_BWD_UNIT_VAR", 0); bwd_split_var = get("DKT_GRAM_BWD_SPLIT_VAR", 11);
-        bwd_unit_mind = get("DKT_GRAM_BWD_UNIT_MIND", 64); bwd_split_mind = get("DKT_GRAM_BWD_SPLIT_MIND", 1024);
-        lds_stage_env_sync();
-    }
-};
-GramEnv& gram_env() {
-    static GramEnv e = [] { GramEnv x; x.load(); return x; }();
-    return e;
-}
+// Measurement / validation switches (dkt_switches.def; values as of the first read / the last dkt_reload_env()); DKT_GRAM_EP_MINB is the one the product reads too
+inline int gram_ep_minb() { return dkt_env_int(DKT_SW_GRAM_EP_MINB, 32); }
+inline bool gram_ep_on() { return dkt_env_int(DKT_SW_GRAM_EP, 1) != 0; }
+inline bool gram_split_on() { return dkt_env_int(DKT_SW_GRAM_SPLIT, 1) != 0; }
 
 template <int NT>
 void launch_sym(const float* Z, float* E, int B, int N, int D, int bk, bool unit, hipStream_t st) {
     if (bk == 3) {
         // <LDS buffers><prefetch depth> of the bf16 split; 2xxx = scaled-f16 split (unit-norm rows only):
         // 2223 = 2 stage buffers, prefetch depth 2, 3 workgroups per CU
-        const int v = unit ? gram_env().unit_var : gram_env().split_var;
+        // Round 4 (tools/sweep_ep_variants.py + the in-step A/B of tools/r4_run12.sh, profiles/r04/v14_ep_variant_sweep.log): the forward with non-temporal Z loads
+        // (22232: -1 % at D = 1600, -5 % at D = 512, -4 % at D = 64 against 2223)
+        const int v = unit ? dkt_env_int(DKT_SW_GRAM_UNIT_VAR, 22232) : dkt_env_int(DKT_SW_GRAM_SPLIT_VAR, 11);
 #ifdef DKT_TWINS             // the pipeline variants the defaults were chosen from (A/B runs, bitwise-twin tests)
         if (v == 21) { hipLaunchKernelGGL((gram_sym_ep_split_kernel<NT, 2, 1>), dim3(B), dim3(256), 0, st, Z, E, N, D); return; }
         if (v == 611) { hipLaunchKernelGGL((gram_sym_ep_split_kernel<NT, 1, 1, 64>), dim3(B), dim3(256), 0, st, Z, E, N, D); return; }
@@ -825,7 +803,7 @@ void launch_sym(const float* Z, float* E, int B, int N, int D, int bk, bool unit
         // the product: unit rows -> scaled 2-way f16 split, 2 stage buffers, prefetch depth 2, 3 workgroups per CU, non-temporal Z loads (22232);
         // any rows -> exact 3-way bf16 split, 1 buffer, depth 1 (11)
         // (NT = 8 at TWO workgroups per CU: built for three it spills 24 registers into the slab loop, and every scratch reload is a `vmcnt(0)` that drains the prefetch)
-        if (v == 22232) hipLaunchKernelGGL((gram_sym_ep_split_kernel<NT, 2, 2, 32, 2, NT == 8 ? 2 : 3, 2>), dim3(B), dim3(256), dkt_lds_pad("DKT_PAD_GRAM_EP"), st, Z, E, N, D);
+        if (v == 22232) hipLaunchKernelGGL((gram_sym_ep_split_kernel<NT, 2, 2, 32, 2, NT == 8 ? 2 : 3, 2>), dim3(B), dim3(256), dkt_lds_pad(DKT_SW_PAD_GRAM_EP), st, Z, E, N, D);
         else hipLaunchKernelGGL((gram_sym_ep_split_kernel<NT, 1, 1>), dim3(B), dim3(256), 0, st, Z, E, N, D);
         return;
     }
@@ -839,7 +817,9 @@ template <int NT>
 void launch_bwd(const float* W, const float* Z, float* dZ, int B, int N, int D, const float* sc, int bd, bool unit, hipStream_t st) {
     if (bd == 3) {
         // <LDS buffers><prefetch depth> of the bf16 split; 2xx = scaled-f16 split (unit-norm rows of Z only)
-        int v = unit ? gram_env().bwd_unit_var : gram_env().bwd_split_var;
+        // Round 4 (the same sweep): below D = 1024, the backward with ONE LDS image and prefetch depth 1 (211: 0.20 vs 0.24 ms at cfg1, 0.57 vs 0.68 ms at cfg3;
+        // equal at D = 1600, where 1222 -- two images, non-temporal dZ stores -- stays): 0 = this choice by D.
+        int v = unit ? dkt_env_int(DKT_SW_GRAM_BWD_UNIT_VAR, 0) : dkt_env_int(DKT_SW_GRAM_BWD_SPLIT_VAR, 11);
         if (unit && v == 0) v = D < 1024 ? 211 : 1222;
 #ifdef DKT_TWINS
         if (v == 222) { hipLaunchKernelGGL((gram_bwd_ep_f16x2_kernel<NT, 2, 2>), dim3(B), dim3(64 * NT), 0, st, W, Z, dZ, N, D, sc); return; }
@@ -852,8 +832,8 @@ void launch_bwd(const float* W, const float* Z, float* dZ, int B, int N, int D, 
         }
 #endif
         // the product: unit rows -> f16 split, one LDS image below D = 1024 (211), two + non-temporal dZ stores from there (1222); any rows -> bf16 split (11)
-        if (v == 1222) { hipLaunchKernelGGL((gram_bwd_ep_f16x2_kernel<NT, 2, 2, 1>), dim3(B), dim3(64 * NT), dkt_lds_pad("DKT_PAD_GRAM_EP_BWD"), st, W, Z, dZ, N, D, sc); return; }
-        if (v == 211) { hipLaunchKernelGGL((gram_bwd_ep_f16x2_kernel<NT, 1, 1>), dim3(B), dim3(64 * NT), dkt_lds_pad("DKT_PAD_GRAM_EP_BWD"), st, W, Z, dZ, N, D, sc); return; }
+        if (v == 1222) { hipLaunchKernelGGL((gram_bwd_ep_f16x2_kernel<NT, 2, 2, 1>), dim3(B), dim3(64 * NT), dkt_lds_pad(DKT_SW_PAD_GRAM_EP_BWD), st, W, Z, dZ, N, D, sc); return; }
+        if (v == 211) { hipLaunchKernelGGL((gram_bwd_ep_f16x2_kernel<NT, 1, 1>), dim3(B), dim3(64 * NT), dkt_lds_pad(DKT_SW_PAD_GRAM_EP_BWD), st, W, Z, dZ, N, D, sc); return; }
         if constexpr (NT <= 7) {                              // one stage buffer must also hold the N x N staging copy of W
             if (v == 11) { hipLaunchKernelGGL((gram_bwd_ep_bf16x3_kernel<NT, 1, 1>), dim3(B), dim3(64 * NT), 0, st, W, Z, dZ, N, D, sc); return; }
         }
@@ -870,10 +850,10 @@ void launch_bwd(const float* W, const float* Z, float* dZ, int B, int N, int D, 
 
 // Returns true when the episode-resident kernel was launched.
 bool dkt_gram_sym_ep_launch(const float* Z, float* E, int B, int N, int D, bool unit, hipStream_t st) {
-    if (N <= 64 || N > 128 || (D & 3) || ((uintptr_t)Z & 15) || gram_env().ep == 0) return false;
-    if (B < gram_env().minb) return false;
+    if (N <= 64 || N > 128 || (D & 3) || ((uintptr_t)Z & 15) || !gram_ep_on()) return false;
+    if (B < gram_ep_minb()) return false;
     // DKT_GRAM_SPLIT=1 (default): 3-way bf16 split on the bf16 MFMA pipe; 0: exact-fp32 MFMA (BK from DKT_GRAM_EP_BK)
-    const int bk = gram_env().split ? 3 : gram_env().ep_bk;
+    const int bk = gram_split_on() ? 3 : dkt_env_int(DKT_SW_GRAM_EP_BK, 64);
     switch ((N + 15) / 16) {
         case 5: launch_sym<5>(Z, E, B, N, D, bk, unit, st); return true;
         case 6: launch_sym<6>(Z, E, B, N, D, bk, unit, st); return true;
@@ -890,16 +870,17 @@ bool dkt_gram_sym_ep_launch(const float* Z, float* E, int B, int N, int D, bool 
 // 16 episodes 0.209 ms, 48: 0.245 ms.)
 bool dkt_gram_fewep_applies(int B, int N, int D) {
     // (N <= 128: the range of the episode-resident kernels it stands in for; larger episodes keep the 64 x 64-tile kernels of dkt_gram_big.hip at every batch)
-    return gram_env().fewep != 0 && (D & 3) == 0 && N <= 128 && B < gram_env().minb;
+    return dkt_env_int(DKT_SW_GRAM_FEWEP, 1) != 0 && (D & 3) == 0 && N <= 128 && B < gram_ep_minb();
 }
 
 bool dkt_gram_bwd_ep_launch(const float* W, const float* Z, float* dZ, int B, int N, int D, const float* sc, bool unit, hipStream_t st) {
-    if (N <= 64 || N > 128 || (D & 3) || ((uintptr_t)Z & 15) || ((uintptr_t)dZ & 15) || gram_env().ep == 0) return false;
-    if (B < gram_env().minb) return false;
+    if (N <= 64 || N > 128 || (D & 3) || ((uintptr_t)Z & 15) || ((uintptr_t)dZ & 15) || !gram_ep_on()) return false;
+    if (B < gram_ep_minb()) return false;
+    lds_stage_env_sync();                     // (twins library: DKT_LDS_STAGE_OLD of the prologues below)
     // the split kernel pays a per-episode setup (A-fragment split, LDS zero fill): it wins from ~16 slabs of 64 features
     // (the f16 kernel for unit-norm rows has the cheaper staging path and already wins at D = 64: 0.27 vs 0.40 ms per 8192 episodes)
-    const int mind = unit ? gram_env().bwd_unit_mind : gram_env().bwd_split_mind;
-    const int bd = (gram_env().split && D >= mind) ? 3 : gram_env().ep_bd;
+    const int mind = unit ? dkt_env_int(DKT_SW_GRAM_BWD_UNIT_MIND, 64) : dkt_env_int(DKT_SW_GRAM_BWD_SPLIT_MIND, 1024);
+    const int bd = (gram_split_on() && D >= mind) ? 3 : dkt_env_int(DKT_SW_GRAM_EP_BD, 32);
     switch ((N + 15) / 16) {
         case 5: launch_bwd<5>(W, Z, dZ, B, N, D, sc, bd, unit, st); return true;
         case 6: launch_bwd<6>(W, Z, dZ, B, N, D, sc, bd, unit, st); return true;
@@ -909,18 +890,9 @@ bool dkt_gram_bwd_ep_launch(const float* W, const float* Z, float* dZ, int B, in
     }
 }
 
-// Re-read the measurement switches (tests / A-B tools flip them inside one process).  Not part of include/dkt_abi.h.
-void dkt_mll_h2_reload_env();          // dkt_mll_h2.hip: DKT_MLL_H2E_MINB
-void dkt_mll_tiled_reload_env();       // dkt_mll_tiled.hip: DKT_MLL_TILED_F16
-void dkt_frontend_reload_env();         // dkt_frontend.hip: DKT_GRAM_EP_MINB / DKT_GRAM_DIST_EP of the episode-resident distance build
-void dkt_mll_reload_env();              // dkt_mll.hip: DKT_MLL_F32MFMA, DKT_MLL_P2_GUARD
-void dkt_gram_big_reload_env();         // dkt_gram_big.hip: DKT_GRAM_BIG_EP
-void dkt_classkernel_reload_env();      // dkt_classkernel.hip: DKT_CLASS_BWD_V4
-void dkt_gram_small_reload_env();       // dkt_gram_small.hip: DKT_GRAM_SMALL_WG
-extern "C" void dkt_reload_env(void) {
-    gram_env().load(); dkt_mll_h2_reload_env(); dkt_mll_tiled_reload_env(); dkt_frontend_reload_env(); dkt_mll_reload_env(); dkt_gram_big_reload_env();
-    dkt_classkernel_reload_env(); dkt_gram_small_reload_env();
-}
+// include/dkt_abi.h: retake the snapshot of the environment switches (every switch of dkt_switches.def, whichever file reads it) / what the snapshot holds
+extern "C" void dkt_reload_env(void) { dkt_env_reload(); }
+extern "C" const char* dkt_env_value(const char* name) { return dkt_env_by_name(name); }
 
 // DKT_GRAM_SPLIT (default 1): the split-precision kernels may be used (0: exact-fp32 MFMA kernels everywhere) -- for dkt_gram_big.hip
-bool dkt_gram_split_enabled() { return gram_env().split != 0; }
+bool dkt_gram_split_enabled() { return gram_split_on(); }

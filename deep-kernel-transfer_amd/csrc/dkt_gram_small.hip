@@ -269,15 +269,10 @@ __global__ __launch_bounds__(WGT > 4 ? 64 * WGT : 256) void gram_small_bwd_kerne
 // A/B (tools/small_wg_ab.py, profiles/r05/v7_small_wg_ab.log; per 8192 tasks): backward 19 x 2916 0.941 -> 0.830 ms, 10 x 2916 0.488 -> 0.402, 25 x 1600
 // 0.514 -> 0.492, 19 x 512 0.130 -> 0.133, 25 x 64 0.035 -> 0.068: from 1024 features.  Forward: equal at 8192 tasks of 19 x 2916 (0.441 / 0.438 ms),
 // 0.076 -> 0.053 ms at 1024 tasks, 25 x 1600 0.261 -> 0.271: from 2048 features.  Twins library: DKT_GRAM_SMALL_WG=0 / 1 forces either form.
-static int g_small_wg = -2;
-void dkt_gram_small_reload_env() { g_small_wg = -2; }
-static unsigned small_lds_pad() {                    // twins library: DKT_GRAM_SMALL_LDS = bytes of (unused) dynamic LDS per workgroup (the occupancy A/B; the backward's default: 56 KB)
-    const char* v = dkt_variant_env("DKT_GRAM_SMALL_LDS");
-    return v ? (unsigned)atoi(v) : 0u;
-}
+static unsigned small_lds_pad() { return dkt_lds_pad(DKT_SW_GRAM_SMALL_LDS); }      // twins library: DKT_GRAM_SMALL_LDS = bytes of (unused) dynamic LDS per workgroup (the occupancy A/B; the backward's default: 56 KB)
 static int small_wgt(int D, int mind) {             // waves per task: 0 (a wave per task), 4, 8 (twins library, DKT_GRAM_SMALL_WG=2: measured, not the default)
-    if (g_small_wg == -2) { const char* v = dkt_variant_env("DKT_GRAM_SMALL_WG"); g_small_wg = v ? atoi(v) : -1; }
-    if (g_small_wg >= 0) return g_small_wg == 0 ? 0 : g_small_wg == 2 ? 8 : g_small_wg == 3 ? 16 : 4;     // (2, 3: eight / sixteen waves per task, twins library only)
+    const int wg = dkt_env_int(DKT_SW_GRAM_SMALL_WG, -1);
+    if (wg >= 0) return wg == 0 ? 0 : wg == 2 ? 8 : wg == 3 ? 16 : 4;     // (2, 3: eight / sixteen waves per task, twins library only)
     return D >= mind ? 4 : 0;
 }
 
@@ -291,12 +286,11 @@ bool dkt_gram_small_launch(const float* Z, float* E, int B, int N, int D, int ki
     // rows beyond sixteen on the VALU: the default for RBF (tools/small_xr_ab.py, profiles/r06/small_xr_ab.log; per 8192 tasks of 19 x 2916 0.396 -> 0.394 ms, 20 x 2916
     // 0.398 -> 0.372, 19 x 512 0.074 -> 0.071, 1024 tasks of 19 x 2916 0.049 -> 0.040); the linear kernel (no row shift on the VALU) measured 0.369 -> 0.387 and keeps
     // its MFMA tiles.  Twins library: DKT_GRAM_SMALL_XR = 0 / 1 = neither / both kinds.
-    bool xr_on = kind == DKT_KERNEL_RBF;
-    { const char* v = dkt_variant_env("DKT_GRAM_SMALL_XR"); if (v) xr_on = atoi(v) != 0; }
+    const bool xr_on = dkt_env_int(DKT_SW_GRAM_SMALL_XR, kind == DKT_KERNEL_RBF) != 0;
     const int xr = (xr_on && N > 16 && N <= 20 && (wgt == 0 || wgt == 4) && kind != DKT_KERNEL_SQDIST) ? (N <= 19 ? 3 : 4) : 0;
     // the XR instance of the four-wave kernel (91 registers: five workgroups per CU) streams best at THREE per CU once every CU has a queue of tasks (tools/small_pf_ab.py,
     // profiles/r06/small_pf_ab.log: 8192 tasks of 19 x 2916 0.381 -> 0.357 ms, 0.386 at two; 1024 tasks: 0.039 -> 0.043, no cap there): 40 KB of untouched dynamic LDS
-    if (xr && wgt == 4 && B >= 4096 && !dkt_variant_env("DKT_GRAM_SMALL_LDS")) pad = 40960u;
+    if (xr && wgt == 4 && B >= 4096 && !dkt_env(DKT_SW_GRAM_SMALL_LDS)) pad = 40960u;
 #define DKT_SM_LAUNCH(K)                                                                                              \
     do {                                                                                                              \
         if (N <= 16) hipLaunchKernelGGL((gram_small_kernel<K, 1, 0>), grid, block, pad, st, Z, E, B, N, D, lengthscale);   \
@@ -345,7 +339,7 @@ bool dkt_gram_small_bwd_launch(const float* W, const float* Z, float* dZ, int B,
     // for the DRAM pages) -- so the launch reserves 56 KB of dynamic LDS it never touches: at most two workgroups per CU.  Bitwise the same results.
     unsigned pad = wgt == 4 ? 57344u : 0u;
 #ifdef DKT_TWINS
-    if (dkt_variant_env("DKT_GRAM_SMALL_LDS")) pad = small_lds_pad();
+    if (dkt_env(DKT_SW_GRAM_SMALL_LDS)) pad = small_lds_pad();
     if (wgt == 8) hipLaunchKernelGGL(gram_small_bwd_kernel<8>, dim3(B), dim3(512), pad, st, W, Z, dZ, B, N, D, sc);
     else if (wgt == 16) hipLaunchKernelGGL(gram_small_bwd_kernel<16>, dim3(B), dim3(1024), pad, st, W, Z, dZ, B, N, D, sc);
     else

@@ -232,18 +232,8 @@ static int mll_generic_lds_launch(const MllArgs& a, hipStream_t st) {
     return mll_status();
 }
 
-static int g_mll_env_read = 0, g_p2_guard = 1, g_force_f32mfma = 0;
-void dkt_mll_reload_env() { g_mll_env_read = 0; }         // dkt_reload_env()
-static void mll_read_env() {
-    if (g_mll_env_read) return;
-    const char* pg = dkt_variant_env("DKT_MLL_P2_GUARD");      // validation aid: a negative guard forces the grow-on-demand path of dkt_mll_h2.hip
-    g_p2_guard = pg ? atoi(pg) : 1;
-    const char* fm = getenv("DKT_MLL_F32MFMA");       // process-wide DKT_MLL_FORCE_F32MFMA: exact-fp32 tile products for every N <= 127 call
-    g_force_f32mfma = (fm && fm[0] == '1') ? 1 : 0;
-    g_mll_env_read = 1;
-}
-static int mll_p2_guard() { mll_read_env(); return g_p2_guard; }
-static bool mll_force_f32mfma() { mll_read_env(); return g_force_f32mfma != 0; }
+static int mll_p2_guard() { return dkt_env_int(DKT_SW_MLL_P2_GUARD, 1); }              // validation aid: a negative guard forces the grow-on-demand path of dkt_mll_h2.hip
+static bool mll_force_f32mfma() { return dkt_env_is(DKT_SW_MLL_F32MFMA, '1'); }        // process-wide DKT_MLL_FORCE_F32MFMA: exact-fp32 tile products for every N <= 127 call
 
 // THE dispatch of dkt_mll_f32, for the workspace query and the launch alike (host arithmetic only): the first route, in the order below, that applies to (B, C, N,
 // flags) and whose scratch fits in avail_bytes.  The query asks with SIZE_MAX; the launch with what the caller brought, so that a short or missing workspace falls to

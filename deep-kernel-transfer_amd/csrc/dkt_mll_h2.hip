@@ -1287,11 +1287,7 @@ void mll_h2e_kernel(MllArgs a) {
 
 // Batch size from which the wave-per-episode kernel serves the training call (below, one episode's classes run in parallel on five
 // waves of the wave-per-matrix kernel).  DKT_MLL_H2E_MINB overrides (A/B runs, tests).
-int g_h2e_minb = -1;
-int h2e_min_batch() {
-    if (g_h2e_minb < 0) { const char* e = getenv("DKT_MLL_H2E_MINB"); g_h2e_minb = e ? atoi(e) : 1024; }
-    return g_h2e_minb;
-}
+int h2e_min_batch() { return dkt_env_int(DKT_SW_MLL_H2E_MINB, 1024); }
 
 template <int NT>
 void launch_h2(const MllArgs& a, hipStream_t st) {
@@ -1317,8 +1313,6 @@ void launch_h2(const MllArgs& a, hipStream_t st) {
 }
 
 }  // namespace
-
-void dkt_mll_h2_reload_env() { g_h2e_minb = -1; }        // dkt_reload_env(): tests / A-B tools flip DKT_MLL_H2E_MINB inside one process
 
 // The calls these kernels serve: N + 1 <= 128 (8 tiles), no Cholesky output, no exact-fp32 request.
 bool dkt_mll_h2_serves(int N, unsigned flags) { return N + 1 <= 128 && !(flags & (DKT_MLL_WANT_CHOL | DKT_MLL_FORCE_F32MFMA)); }

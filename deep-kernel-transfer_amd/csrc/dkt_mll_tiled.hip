@@ -1348,59 +1348,16 @@ inline bool invres_fits(const WRanges& r, const int NT) {
     return true;
 }
 
-int g_tiled_wnw = -1;
 inline int tiled_wnw() {                   // DKT_MLL_TILED_WNW: waves per workgroup of the W kernel (4: two workgroups per CU; 8: one, wider column ranges; 84: 8 for the first range, 4 for the rest; 0 / unset: by NT)
-    if (g_tiled_wnw < 0) {
-        const char* v = dkt_variant_env("DKT_MLL_TILED_WNW");
-        const int w = v ? atoi(v) : 0;
-        g_tiled_wnw = (w == 8 || w == 4 || w == 84) ? w : 0;
-    }
-    return g_tiled_wnw;
+    const int w = dkt_env_int(DKT_SW_MLL_TILED_WNW, 0);
+    return (w == 8 || w == 4 || w == 84) ? w : 0;
 }
-int g_tiled_wdma = -1;
-inline bool tiled_wdma() {
-    if (g_tiled_wdma < 0) {
-        const char* v = dkt_variant_env("DKT_MLL_TILED_WDMA");
-        g_tiled_wdma = (v && v[0] == '0') ? 0 : 1;
-    }
-    return g_tiled_wdma != 0;
-}
-
-int g_tiled_wgs = -1;
-inline int tiled_wgs() {
-    if (g_tiled_wgs < 0) {
-        const char* v = dkt_variant_env("DKT_MLL_TILED_WGS");
-        g_tiled_wgs = (v && v[0] == '2') ? 2 : 3;
-    }
-    return g_tiled_wgs;
-}
-
-int g_tiled_invres = -1;
-inline bool tiled_invres() {
-    if (g_tiled_invres < 0) {
-        const char* v = dkt_variant_env("DKT_MLL_TILED_INVRES");                      // default OFF: measured at parity with the block-column kernel (7.3 vs 6.5 ms at
-        g_tiled_invres = (v && v[0] == '1') ? 1 : 0;                           // N = 420, 4.0 vs 4.1 at N = 320: 65 short steps per matrix)
-    }
-    return g_tiled_invres != 0;
-}
-
-int g_tiled_wres = -1;
-inline bool tiled_wres() {
-    if (g_tiled_wres < 0) {
-        const char* v = dkt_variant_env("DKT_MLL_TILED_WRES");
-        g_tiled_wres = (v && v[0] == '0') ? 0 : 1;
-    }
-    return g_tiled_wres != 0;
-}
-
-int g_tiled_f16 = -1;
-inline bool tiled_f16() {
-    if (g_tiled_f16 < 0) {
-        const char* v = dkt_variant_env("DKT_MLL_TILED_F16");
-        g_tiled_f16 = (v && v[0] == '0') ? 0 : 1;
-    }
-    return g_tiled_f16 != 0;
-}
+inline bool tiled_wdma() { return dkt_env_on(DKT_SW_MLL_TILED_WDMA); }
+inline int tiled_wgs() { return dkt_env_is(DKT_SW_MLL_TILED_WGS, '2') ? 2 : 3; }
+// default OFF: measured at parity with the block-column kernel (7.3 vs 6.5 ms at N = 420, 4.0 vs 4.1 at N = 320: 65 short steps per matrix)
+inline bool tiled_invres() { return dkt_env_is(DKT_SW_MLL_TILED_INVRES, '1'); }
+inline bool tiled_wres() { return dkt_env_on(DKT_SW_MLL_TILED_WRES); }
+inline bool tiled_f16() { return dkt_env_on(DKT_SW_MLL_TILED_F16); }
 inline int tiled_nt(int N) { return (N + 1 + 15) / 16; }
 inline size_t tiled_ws_floats(int Bc, int C, int N) {
     const size_t nt = tiled_nt(N), ntt = nt * (nt + 1) / 2, nmat = (size_t)Bc * C;
@@ -1409,14 +1366,9 @@ inline size_t tiled_ws_floats(int Bc, int C, int N) {
     return fl > gen ? fl : gen;
 }
 constexpr int TILED_CHUNK_MAX = 1024;      // episodes per pass over the workspace (N = 420, C = 20: 7.7 GB of tiles): the workspace is sized for it
-int g_tiled_chunk = -1;
 inline int tiled_chunk_episodes() {        // DKT_MLL_TILED_CHUNK (measurement aid: <= 1024; a chunk whose tile arrays fit the 256-MB memory-side cache)
-    if (g_tiled_chunk < 0) {
-        const char* v = getenv("DKT_MLL_TILED_CHUNK");
-        const int c = v ? atoi(v) : TILED_CHUNK_MAX;
-        g_tiled_chunk = (c >= 1 && c <= TILED_CHUNK_MAX) ? c : TILED_CHUNK_MAX;
-    }
-    return g_tiled_chunk;
+    const int c = dkt_env_int(DKT_SW_MLL_TILED_CHUNK, TILED_CHUNK_MAX);
+    return (c >= 1 && c <= TILED_CHUNK_MAX) ? c : TILED_CHUNK_MAX;
 }
 
 template <int MC>
@@ -1521,7 +1473,6 @@ void tiled_chunk(const TiledArgs& t, int bcnt, bool grad, hipStream_t st) {
 
 }  // namespace
 
-void dkt_mll_tiled_reload_env() { g_tiled_f16 = -1; g_tiled_chunk = -1; g_tiled_wres = -1; g_tiled_invres = -1; g_tiled_wgs = -1; g_tiled_wdma = -1; g_tiled_wnw = -1; }      // dkt_reload_env()
 
 bool dkt_mll_tiled_supports(int N, unsigned flags, int C) {
 #ifndef DKT_TWINS

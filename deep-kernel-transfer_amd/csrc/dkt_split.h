@@ -131,10 +131,13 @@ __device__ __forceinline__ void sym_tiles_mfma_bf16x3(f32x4* acc, const __bf16* 
 // two loads: 6 - 10 dependent memory round trips per episode at N = 105 (round 5, found in the ISA of the Gram-backward prologues).
 #ifdef DKT_TWINS          // DKT_LDS_STAGE_OLD=1 (twins library): the copy loop this replaced, for same-box A/B runs and the bitwise-twin test
 __device__ int g_lds_stage_old = 0;
+unsigned g_lds_stage_gen = 0;            // dkt_env_generation() as of this translation unit's last copy to the device (0: none yet)
+// The one switch the DEVICE reads: called on the launch path of the kernels that use DKT_LDS_STAGE_OLD_LOOP (never from the reload: it must work without a GPU)
 inline void lds_stage_env_sync() {
-    const char* v = getenv("DKT_LDS_STAGE_OLD");
-    const int f = (v && v[0] == '1') ? 1 : 0;
+    if (g_lds_stage_gen == dkt_env_generation()) return;
+    const int f = dkt_env_is(DKT_SW_LDS_STAGE_OLD, '1') ? 1 : 0;
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lds_stage_old), &f, sizeof(int));
+    g_lds_stage_gen = dkt_env_generation();
 }
 #define DKT_LDS_STAGE_OLD_LOOP(stmt) if (g_lds_stage_old) { stmt } else
 #else

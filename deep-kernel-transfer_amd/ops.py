@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 from typing import Optional
 
 import torch
@@ -129,17 +130,11 @@ class _timed:
 # ------------------------------------------------------------------------------------------------
 # Switches the PRODUCT library reads (dispatch thresholds / the process-wide exact-fp32 request of include/dkt_abi.h); everything else is a variant switch that only
 # the twins library (libdkt_twins.so, -DDKT_TWINS) knows: with DKT_TWINS=1 in the environment AND one of them set, the calls of this module go to that library
-# (tests, A/B tools).  Without DKT_TWINS=1 the variant switches have no effect at all.
-_PRODUCT_SWITCHES = ("DKT_GRAM_EP_MINB", "DKT_MLL_H2E_MINB", "DKT_MLL_TILED_CHUNK", "DKT_MLL_F32MFMA")
-_VARIANT_SWITCHES = ("DKT_GRAM_EP", "DKT_GRAM_SPLIT", "DKT_GRAM_EP_BK", "DKT_GRAM_EP_BD", "DKT_GRAM_UNIT_VAR", "DKT_GRAM_SPLIT_VAR", "DKT_GRAM_BWD_UNIT_VAR",
-                     "DKT_GRAM_BWD_SPLIT_VAR", "DKT_GRAM_BWD_UNIT_MIND", "DKT_GRAM_BWD_SPLIT_MIND", "DKT_MLL_TILED_F16", "DKT_GRAM_DIST_EP", "DKT_MLL_P2_GUARD",
-                     "DKT_MLL_TILED_WRES", "DKT_MLL_TILED_INVRES", "DKT_GRAM_BIG_EP", "DKT_MLL_TILED_WGS", "DKT_GRAM_BWD_ROWS8", "DKT_MLL_TILED_WDMA", "DKT_CLASS_BWD_V4",
-                     "DKT_MLL_TILED_WNW", "DKT_GRAM_SMALL", "DKT_BIG_NB", "DKT_GRAM_BN_F16", "DKT_LDS_STAGE_OLD", "DKT_GRAM_SMALL_WG", "DKT_CLASS_BWD_N128", "DKT_GRAM_FEWEP",
-                     "DKT_GRAM_SMALL_XR", "DKT_GRAM_SMALL_LDS",
-                     # bytes of untouched dynamic LDS on top of a kernel's own (occupancy A/B of the twins library, dkt_lds_pad)
-                     "DKT_PAD_AFFNORM", "DKT_PAD_BAND_BACK", "DKT_PAD_BAND_CLASS", "DKT_PAD_BAND_FWD", "DKT_PAD_CK_BWD", "DKT_PAD_CK_FWD", "DKT_PAD_FE_FWD",
-                     "DKT_PAD_GRAM_BIG_BWD", "DKT_PAD_GRAM_EP", "DKT_PAD_GRAM_EP_BWD", "DKT_PAD_LR_BWD", "DKT_PAD_LR_FIN", "DKT_PAD_LR_GRAM", "DKT_PAD_NBB",
-                     "DKT_PAD_ROWDOT")
+# (tests, A/B tools).  Without DKT_TWINS=1 the variant switches have no effect at all.  The names are the table the libraries themselves read: csrc/dkt_switches.def.
+with open(os.path.join(_lib.CSRC, "dkt_switches.def")) as _fh:
+    _SWITCH_TABLE = re.findall(r"^X\((\w+), (PRODUCT|VARIANT)\)", _fh.read(), re.M)
+_PRODUCT_SWITCHES = tuple("DKT_" + n for n, c in _SWITCH_TABLE if c == "PRODUCT")
+_VARIANT_SWITCHES = tuple("DKT_" + n for n, c in _SWITCH_TABLE if c == "VARIANT")
 _ENV_SWITCHES = _PRODUCT_SWITCHES + _VARIANT_SWITCHES
 _env_seen = {}           # id(lib) -> {switch: value} as of the library's last (re)read of the environment
 

@@ -28,14 +28,15 @@
 extern "C" {
 #endif
 
-#define DKT_ABI_VERSION 7 /* 2 (round 3): + dkt_gram_bn_train_f32, dkt_class_kernel_*, DKT_MLL_E_PER_CLASS (W layout [B,C,N,N]), DKT_MLL_FORCE_F32MFMA; \
+#define DKT_ABI_VERSION 8 /* 2 (round 3): + dkt_gram_bn_train_f32, dkt_class_kernel_*, DKT_MLL_E_PER_CLASS (W layout [B,C,N,N]), DKT_MLL_FORCE_F32MFMA; \
                              3 (round 4): DKT_MLL_E_PER_CLASS up to N = 447, DKT_MLL_FORCE_REG retired (DKT_ERR_BAD_ARG), + dkt_affine_normalize_f32, dkt_normalize_bn_bwd_f32; \
                              4 (round 5): DKT_MLL_E_PER_CLASS for every N with the jitter ladder on every path (+ DKT_MLL_FORCE_GENERIC as its twin), \
                                           + dkt_predict_per_class_f32, dkt_reload_env declared, + dkt_lowrank_* (linear kernels in feature space, D <= 64 < N); \
                              5 (round 6): shared-E calls with 12 <= C <= 32 classes, 128 <= N <= 432 and >= 192 episodes take ONE band reduction per episode (dkt_mll_band.hip); \
                                           + DKT_MLL_FORCE_TILED (the tile-array kernels as its twin), DKT_MLL_FORCE_BAND; the f16-split kernels (N <= 127) are followed by a kappa-aware fix-up launch (DKT_MLL_NO_KAPPA_GUARD); \
                              6 (round 6): + dkt_objective_f32, dkt_hyper_grads_f32; \
-                             7 (round 6): + dkt_bn_param_grads_f32 (+ its workspace query); the kappa test of the f16-split kernels moved into those kernels (one launch less per call) */
+                             7 (round 6): + dkt_bn_param_grads_f32 (+ its workspace query); the kappa test of the f16-split kernels moved into those kernels (one launch less per call); \
+                             8: + dkt_env_value (what dkt_reload_env() read); every switch follows dkt_reload_env(), DKT_BIG_NB included */
 
 /* status codes */
 #define DKT_OK 0
@@ -91,9 +92,13 @@ int dkt_abi_version(void);
  * them; a host that changed one inside a running process (tests, A/B tools) calls this to have them re-read.  No effect on results of the
  * default configuration.  (Exported since round 2; declared here since ABI 4.)
  * Threads: every entry point is re-entrant on its arguments (no buffers, handles or streams are kept between calls); the only process-wide state is this cache of the
- * environment's dispatch thresholds -- plain ints, filled lazily and idempotently (concurrent first calls store the same value), which the environment being per-process
- * makes process-wide by nature.  dkt_reload_env() itself is for single-threaded harnesses: do not call it while another thread is inside a dkt_* call. */
+ * environment's switches -- one snapshot of their values (csrc/dkt_env.h over the table csrc/dkt_switches.def), taken at the first read, which the environment being
+ * per-process makes process-wide by nature.  Every switch is read from that snapshot: a host that changes one and calls the ABI directly calls dkt_reload_env().  dkt_reload_env() itself is for single-threaded harnesses: do not call it while another thread is inside a dkt_* call. */
 void dkt_reload_env(void);
+/* What the snapshot holds for the environment variable DKT_<name> (name without the prefix, e.g. "MLL_H2E_MINB"): the value as of the first read / the last
+ * dkt_reload_env(), cut to 31 characters; NULL when the variable is unset, when the name is not in csrc/dkt_switches.def, or when it names a variant switch and
+ * the library is not a -DDKT_TWINS build.  The pointer is valid until the next dkt_reload_env().  For host tests: what did the reload reach.  (ABI 8) */
+const char* dkt_env_value(const char* name);
 
 /* Device query used by the host side to fail loudly on a non-gfx950 box: returns the number of
  * compute units of the current HIP device (>0) or <0 on error. */

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DKT_X16_ABI_VERSION 1
+#define DKT_X16_ABI_VERSION 2 /* 2: + dkt_x16_env_value */
 
 /* element type of X / dX */
 #define DKT_X_BF16 1
@@ -30,6 +30,8 @@ extern "C" {
 int dkt_x16_abi_version(void);
 /* the library reads the environment switches of dkt_abi.h once; dkt_x16_reload_env() makes it read them again (as dkt_reload_env()) */
 void dkt_x16_reload_env(void);
+/* as dkt_env_value(): what this library's snapshot holds for DKT_<name> (ABI 2) */
+const char* dkt_x16_env_value(const char* name);
 
 /* twin: dkt_bn_stats_f32 */
 int dkt_bn_stats_x16(const void* X, int xdtype, const float* gamma, const float* beta, float eps, float* mean, float* rstd,

@@ -131,7 +131,7 @@ def test_new_symbols_are_in_the_header_the_table_and_the_library(lib):
         proto = re.search(r"\b%s\s*\(([^)]*)\)" % name, header).group(1)
         assert name in L.SIGNATURES and len(L.SIGNATURES[name][1]) == proto.count(",") + 1 and hasattr(lib, name)
     assert L.SOURCES[-2:] == ["dkt_mll_rownoise.hip", "dkt_laplace_grad.hip"] and len(L.LIBS) == 7
-    assert lib.dkt_abi_version() == 7 and L.abi_version_of_header() == 7
+    assert lib.dkt_abi_version() == 8 and L.abi_version_of_header() == 8
     assert lib.dkt_mll_rownoise_workspace_bytes(2, 20, 100) == 2 * 20 * 100 * 100 * 4 and lib.dkt_mll_rownoise_workspace_bytes(0, 5, 25) == 0
     assert lib.dkt_mll_rownoise_workspace_bytes(1, 1, 1) == 4 and lib.dkt_mll_rownoise_workspace_bytes(3, 5, -1) == 0
     null = [None, 0, 0, None, 0, None, 0] + [None] * 10

@@ -27,7 +27,7 @@ EXEMPT = [
 ]
 
 # Names of the signature tables that launch nothing: pure host queries
-HOST_QUERIES = ("abi_version", "device_cu_count", "reload_env", "workspace_bytes", "_supported", "_nsplit", "state_bytes", "augment_plan")
+HOST_QUERIES = ("abi_version", "device_cu_count", "reload_env", "env_value", "workspace_bytes", "_supported", "_nsplit", "state_bytes", "augment_plan")
 
 
 class Case:

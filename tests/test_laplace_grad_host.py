@@ -88,7 +88,7 @@ def test_new_symbols_are_in_the_header_the_table_and_the_library(lib):
         proto = re.search(r"\b%s\s*\(([^)]*)\)" % name, header).group(1)
         assert name in L.SIGNATURES and len(L.SIGNATURES[name][1]) == proto.count(",") + 1 and hasattr(lib, name)
     assert "dkt_laplace_grad.hip" in L.SOURCES and L.SOURCES[-1] == "dkt_laplace_grad.hip"
-    assert lib.dkt_abi_version() == 7 and L.abi_version_of_header() == 7
+    assert lib.dkt_abi_version() == 8 and L.abi_version_of_header() == 8
     assert lib.dkt_laplace_grad_workspace_bytes(2, 20, 100) == 2 * 20 * 100 * 100 * 4 and lib.dkt_laplace_grad_workspace_bytes(0, 5, 25) == 0
     assert lib.dkt_laplace_grad_f32(None, 0, 0, None, None, 0, None, None, None, None, None, 1, 5, 25, None, 0, None) == -1
     usage = json.load(open(os.path.join(L.OBJ_DIR, "libdkt_hip.so.resource_usage.json")))

@@ -36,10 +36,10 @@ def _exports(path):
 
 def test_x16_library_exports_exactly_its_header(x16):
     declared = _declared("dkt_abi_x16.h")
-    assert len(declared) == 8
+    assert len(declared) == 9
     assert sorted(dkt_amd._lib.X16_SIGNATURES) == declared
     assert _exports(dkt_amd._lib.X16_LIB_PATH) == declared
-    assert x16.dkt_x16_abi_version() == dkt_amd._lib.x16_abi_version_of_header() == 1
+    assert x16.dkt_x16_abi_version() == dkt_amd._lib.x16_abi_version_of_header() == 2
     # each entry point is its fp32 twin of dkt_abi.h plus `int xdtype` right after X
     for name, (res, args) in dkt_amd._lib.X16_SIGNATURES.items():
         twin = name.replace("_x16", "_f32")

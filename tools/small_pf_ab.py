@@ -1,6 +1,6 @@
-"""(The DKT_GRAM_SMALL_PF instances were removed after this measurement -- commit 06c82cc has them; the script still sweeps the cap for the shipped depth.)
-A/B of the N <= 32 Gram forward's prefetch depth (dkt_gram_small.hip; twins library): DKT_GRAM_SMALL_PF=8 (eight 16-feature steps in flight per wave instead of four)
-under the workgroups-per-CU cap DKT_GRAM_SMALL_LDS.   python tools/small_pf_ab.py"""
+"""Sweep of the workgroups-per-CU cap DKT_GRAM_SMALL_LDS of the N <= 32 Gram forward (dkt_gram_small.hip; twins library).  (Written as the A/B of the forward's
+prefetch depth under that cap: the eight-steps-in-flight instances were removed after the measurement, profiles/r06/small_pf_ab.log -- commit 06c82cc has them; what
+is left sweeps the cap for the shipped depth.)   python tools/small_pf_ab.py"""
 import importlib
 import os
 import sys
@@ -29,15 +29,12 @@ for (b, n, d, kind) in [(8192, 19, 2916, ops.KERNEL_RBF), (8192, 19, 2916, ops.K
     g = torch.Generator(device=dev).manual_seed(n + d)
     z = torch.randn(b, n, d, device=dev, generator=g) * 0.05
     ls = torch.tensor([1.3], device=dev)
-    res, outs = {}, {}
+    res = {}
+    caps = ("0", "33000", "41000", "54000", "81000")
     for rnd in range(3):
-        for pf in ("4", "8"):
-            for lds in ("0", "33000", "41000", "54000", "81000"):
-                os.environ["DKT_GRAM_SMALL_PF"], os.environ["DKT_GRAM_SMALL_LDS"] = pf, lds
-                ms, e = timed(lambda: ops.gram(z, None, kind, ls if kind != ops.KERNEL_LINEAR else None))
-                res.setdefault((pf, lds), []).append(ms)
-                outs[pf] = e
-    del os.environ["DKT_GRAM_SMALL_PF"], os.environ["DKT_GRAM_SMALL_LDS"]
-    print("B=%d N=%d D=%d kind=%d  (columns: at most all / 4 / 3 / 2 / 1 workgroups per CU)  %s" % (b, n, d, kind, "bitwise equal" if torch.equal(outs["4"], outs["8"]) else "DIFFER"))
-    for pf in ("4", "8"):
-        print("   %s steps in flight: %s" % (pf, "  ".join("%.4f" % min(res[(pf, l)]) for l in ("0", "33000", "41000", "54000", "81000"))), flush=True)
+        for lds in caps:
+            os.environ["DKT_GRAM_SMALL_LDS"] = lds
+            ms, _ = timed(lambda: ops.gram(z, None, kind, ls if kind != ops.KERNEL_LINEAR else None))
+            res.setdefault(lds, []).append(ms)
+    del os.environ["DKT_GRAM_SMALL_LDS"]
+    print("B=%d N=%d D=%d kind=%d  (columns: at most all / 4 / 3 / 2 / 1 workgroups per CU)  %s" % (b, n, d, kind, "  ".join("%.4f" % min(res[l]) for l in caps)), flush=True)

@@ -1,5 +1,4 @@
-"""(The "c" column = DKT_GRAM_SMALL_COAL, coalesced loads + a lane transpose, was removed after this measurement -- commit 06c82cc has it; the switch is ignored now.)
-A/B of the N <= 32 Gram forward with the rows beyond sixteen on the VALU (dkt_gram_small.hip, template parameter XR; 17 <= N <= 20: the QMUL head's 19 frames) against
+"""A/B of the N <= 32 Gram forward with the rows beyond sixteen on the VALU (dkt_gram_small.hip, template parameter XR; 17 <= N <= 20: the QMUL head's 19 frames) against
 the three-MFMA-tile form (twins library, DKT_GRAM_SMALL_XR=0); errors of both against float64.   python tools/small_xr_ab.py"""
 import importlib
 import os
@@ -32,23 +31,19 @@ for (b, n, d, kind) in [(8192, 19, 2916, ops.KERNEL_RBF), (8192, 19, 2916, ops.K
     ls = torch.tensor([1.3], device=dev)
     fw, outs = {}, {}
     for rnd in range(3):
-        for v in ("0", "1", "c"):
-            os.environ["DKT_GRAM_SMALL_XR"] = "1" if v == "c" else v                      # "c": coalesced loads + the lane transpose (DKT_GRAM_SMALL_COAL=1)
-            os.environ["DKT_GRAM_SMALL_COAL"] = "1" if v == "c" else "0"
-            if v == "c" and kind == ops.KERNEL_LINEAR:
-                os.environ["DKT_GRAM_SMALL_XR"] = "0"
+        for v in ("0", "1"):
+            os.environ["DKT_GRAM_SMALL_XR"] = v
             ms, e = timed(lambda: ops.gram(z, None, kind, ls if kind != ops.KERNEL_LINEAR else None))
             fw.setdefault(v, []).append(ms)
             outs[v] = e
-    del os.environ["DKT_GRAM_SMALL_XR"], os.environ["DKT_GRAM_SMALL_COAL"]
+    del os.environ["DKT_GRAM_SMALL_XR"]
     zd = z[:256].double()
     ref = zd @ zd.transpose(1, 2)
     if kind == ops.KERNEL_RBF:
         dg = torch.diagonal(ref, dim1=1, dim2=2)
         ref = torch.exp(-0.5 * (dg.unsqueeze(2) + dg.unsqueeze(1) - 2 * ref).clamp_min(0) / 1.3 ** 2)
-    err = {v: ((outs[v][:256].double() - ref).abs().max() / ref.abs().max()).item() for v in ("0", "1", "c")}
+    err = {v: ((outs[v][:256].double() - ref).abs().max() / ref.abs().max()).item() for v in ("0", "1")}
     sym = bool(torch.equal(outs["1"], outs["1"].transpose(1, 2)))
     af = b * (n * d + n * n) * 4
-    print("B=%d N=%d D=%d kind=%d  MFMA tiles %.4f ms (%.3f of 8 TB/s, err %.1e)   extra rows on the VALU %.4f ms (%.3f, err %.1e, %s)   coalesced loads + lane transpose %.4f ms (%.3f, err %.1e, %s)"
-          % (b, n, d, kind, min(fw["0"]), af / min(fw["0"]) / 8e9, err["0"], min(fw["1"]), af / min(fw["1"]) / 8e9, err["1"], "symmetric" if sym else "NOT SYMMETRIC",
-             min(fw["c"]), af / min(fw["c"]) / 8e9, err["c"], "bitwise = its form without" if torch.equal(outs["c"], outs["1" if kind == ops.KERNEL_RBF and 16 < n <= 19 else "0"]) else "differs"), flush=True)
+    print("B=%d N=%d D=%d kind=%d  MFMA tiles %.4f ms (%.3f of 8 TB/s, err %.1e)   extra rows on the VALU %.4f ms (%.3f, err %.1e, %s)"
+          % (b, n, d, kind, min(fw["0"]), af / min(fw["0"]) / 8e9, err["0"], min(fw["1"]), af / min(fw["1"]) / 8e9, err["1"], "symmetric" if sym else "NOT SYMMETRIC"), flush=True)
