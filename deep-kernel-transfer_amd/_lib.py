@@ -20,6 +20,10 @@ An object file's cache key hashes its source, every csrc/*.h, csrc/*.inc and csr
 include -- so an edit to one library's header recompiles that library only.
 
 Adding a library: one ABI header under include/, one signature dict, one `LibSpec` entry in `LIBS` (+ the one-line `load_*` / `build_*` names its callers want).
+
+Beside the table, `EXT_LIBS`: extension libraries, product code whose sources live under csrc_ext/ (`LibSpec.src_dir`; they include the headers of csrc/) and which go
+through the same operations:
+  loo    libdkt_loo.so    the leave-one-out predictive likelihood and its gradients (include/dkt_abi_loo.h; docs/LOO.md).
 """
 from __future__ import annotations
 
@@ -141,6 +145,13 @@ DIAG_SIGNATURES = {
     "dkt_diag_mll_reg_f32": (_c_i, [_c_p, _c_p, ctypes.c_long, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_f, _c_i, ctypes.c_uint] + [_c_p] * 11),
 }
 
+# libdkt_loo.so (include/dkt_abi_loo.h; tests check that this lists every function of the header): an extension library, EXT_LIBS below
+LOO_SIGNATURES = {
+    "dkt_loo_abi_version": (_c_i, []),
+    "dkt_loo_f32": (_c_i, [_c_p, ctypes.c_long, ctypes.c_long, _c_p, ctypes.c_long] + [_c_p] * 4 + [_c_i, _c_i, _c_i, _c_f, _c_i, ctypes.c_uint] + [_c_p] * 11),
+}
+LOO_MAX_N, LOO_MAX_C = 127, 32      # the limits of include/dkt_abi_loo.h (DKT_ERR_SHAPE outside them)
+
 
 class LibSpec(NamedTuple):
     """What differs between the libraries; everything below takes one of these."""
@@ -154,6 +165,7 @@ class LibSpec(NamedTuple):
     reload_symbol: Optional[str] = None     # makes the library re-read its environment switches (ops._sync_env)
     twins: bool = False                     # compiled with -DDKT_TWINS
     spill_budget: bool = True               # SPILL_BUDGET fails the build: product code (not the twins' non-default instantiations, not measurement kernels)
+    src_dir: Optional[str] = None           # where `sources` live when not under csrc/ (an extension library: EXT_LIBS)
 
 
 def _so(stem: str) -> str:
@@ -174,6 +186,14 @@ LIBS = {
                    "dkt_gpc_abi_version"),
     "diag": LibSpec(_so("diag"), ["dkt_diag.hip", "dkt_mll_reg_twin.hip"], DIAG_SIGNATURES, "the measurement kernels have no fallback.", spill_budget=False),
 }
+# Extension libraries: product code that stands beside the table of seven (sources under csrc_ext/, which may include the headers of csrc/), built by build_loo()
+# and on first load; the operations below take their specs like any other.
+CSRC_EXT = os.path.join(_HERE, "csrc_ext")
+EXT_LIBS = {
+    "loo": LibSpec(_so("loo"), ["dkt_loo.hip"], LOO_SIGNATURES, "the leave-one-out objective has no fallback.", "dkt_abi_loo.h", "DKT_LOO_ABI_VERSION",
+                   "dkt_loo_abi_version", src_dir=CSRC_EXT),
+}
+LOO_LIB_PATH = EXT_LIBS["loo"].path
 LIB_PATH, TWINS_LIB_PATH, X16_LIB_PATH, DATA_LIB_PATH, SMK_LIB_PATH, GPC_LIB_PATH, DIAG_LIB_PATH = (LIBS[k].path for k in ("hip", "twins", "x16", "data", "smk", "gpc", "diag"))
 
 _lock = threading.Lock()
@@ -253,7 +273,8 @@ def _digest(src: str, spec: LibSpec) -> str:
     """Content hash of a source, the headers it can include (every csrc/*.h, *.inc and *.def, include/dkt_abi.h, its library's own ABI header) and the flags: the
     object cache key (mtimes do not survive a checkout)."""
     import hashlib
-    headers = (sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc", ".def"))) +
+    dirs = [CSRC] + ([spec.src_dir] if spec.src_dir else [])          # (an extension library's sources include csrc/'s headers and their own directory's)
+    headers = (sorted(os.path.join(d, f) for d in dirs for f in os.listdir(d) if f.endswith((".h", ".inc", ".def"))) +
                [os.path.join(INCLUDE, f) for f in sorted({"dkt_abi.h", spec.header} - {None})])
     h = hashlib.sha256()
     for f in [src] + headers:
@@ -262,8 +283,12 @@ def _digest(src: str, spec: LibSpec) -> str:
     return h.hexdigest()[:20]
 
 
+def _src(spec: LibSpec, name: str, replace=None) -> str:
+    return (replace or {}).get(name, os.path.join(spec.src_dir or CSRC, name))
+
+
 def _stamp(spec: LibSpec, replace=None) -> str:
-    return ";".join(_digest((replace or {}).get(s, os.path.join(CSRC, s)), spec) for s in spec.sources)
+    return ";".join(_digest(_src(spec, s, replace), spec) for s in spec.sources)
 
 
 def _stale(spec: LibSpec) -> bool:
@@ -285,7 +310,7 @@ def _compile_link(spec: LibSpec, target: str = None, replace=None, verbose=False
     os.makedirs(OBJ_DIR, exist_ok=True)
 
     def one(name):
-        src = (replace or {}).get(name, os.path.join(CSRC, name))
+        src = _src(spec, name, replace)
         obj = os.path.join(OBJ_DIR, "%s.%s.o" % (os.path.basename(src), _digest(src, spec)))
         if not os.path.exists(obj) or not os.path.exists(obj + ".res.json"):
             cmd = [hipcc] + _flags(spec.twins) + ["-c", src, "-o", obj + ".tmp"]
@@ -329,7 +354,7 @@ def _compile_link(spec: LibSpec, target: str = None, replace=None, verbose=False
             if f.endswith(".objects.json"):
                 with open(os.path.join(OBJ_DIR, f)) as fh:
                     keep.update(json.load(fh))
-        known = {src for lib in LIBS.values() for src in lib.sources}
+        known = {src for lib in list(LIBS.values()) + list(EXT_LIBS.values()) for src in lib.sources}
         for f in os.listdir(OBJ_DIR):
             base = f[:-len(".res.json")] if f.endswith(".res.json") else f
             if base.endswith(".o") and base not in keep and any(base.startswith(src + ".") for src in known):
@@ -385,6 +410,10 @@ def build_diag(verbose: bool = False) -> str:
     return _build_if_stale(LIBS["diag"], verbose)
 
 
+def build_loo(verbose: bool = False) -> str:
+    return _build_if_stale(EXT_LIBS["loo"], verbose)
+
+
 def _header_version(spec: LibSpec) -> int:
     """The ABI version as the library's header under include/ declares it."""
     import re
@@ -410,6 +439,10 @@ def smk_abi_version_of_header() -> int:
 
 def gpc_abi_version_of_header() -> int:
     return _header_version(LIBS["gpc"])
+
+
+def loo_abi_version_of_header() -> int:
+    return _header_version(EXT_LIBS["loo"])
 
 
 def device_code_objects(path: str = None) -> list:
@@ -601,6 +634,10 @@ def load_gpc() -> ctypes.CDLL:
 
 def load_diag() -> ctypes.CDLL:
     return _load(LIBS["diag"])
+
+
+def load_loo() -> ctypes.CDLL:
+    return _load(EXT_LIBS["loo"])
 
 
 def reload_env(lib) -> None:

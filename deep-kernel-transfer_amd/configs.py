@@ -14,6 +14,10 @@ amp = None
 # `--likelihood` of the evaluation drivers sets it (io_utils.parse_args('test')), for the same reason as amp: test_uncertainty.py does not pass the flag on.
 likelihood = None
 
+# objective of the DKT / DKTRegression models a process builds when their constructor is not told (objective=None): None (= 'mll', the marginal likelihood) or
+# 'loo' (the leave-one-out predictive likelihood, docs/LOO.md; Gaussian likelihood only).  `--objective` of train.py / test.py sets it (io_utils.parse_args).
+objective = None
+
 save_dir = './save/'                     # checkpoints: <save_dir>checkpoints/<dataset>/<model>_<method>[_aug]_<n>way_<k>shot
 
 # file-list roots of the image datasets (image_data.FilelistEpisodeLoader; `--dataset synthetic` needs none)

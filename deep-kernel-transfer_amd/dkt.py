@@ -164,6 +164,23 @@ class _MetaBatched:
 
 
 LIKELIHOODS = ("gaussian", "bernoulli", "dirichlet")
+OBJECTIVES = ("mll", "loo")
+
+
+def objective_name(objective):
+    """objective=None | "mll" | "loo" -> "mll" | "loo" (None: configs.objective, the drivers' --objective; "mll" by default)."""
+    objective = objective or configs.objective or "mll"
+    if objective not in OBJECTIVES:
+        raise ValueError("objective must be one of %s, got %r" % (OBJECTIVES, objective))
+    return objective
+
+
+def check_loo_rows(n, c=1, rows="n_way * (n_support + n_query)"):
+    """The limits of the LDS-resident kernel behind objective="loo" (dkt_loo_f32): 127 rows, 32 classes.  Raised on the host, before any launch."""
+    if c > ops._lib.LOO_MAX_C:
+        raise ValueError("objective='loo' takes up to %d classes, the episode has %d" % (ops._lib.LOO_MAX_C, c))
+    if n > ops._lib.LOO_MAX_N:
+        raise ValueError("objective='loo' takes episodes of up to %d rows (%s), this one has %d" % (ops._lib.LOO_MAX_N, rows, n))
 
 
 class _GraphedTrainStep:
@@ -211,7 +228,7 @@ class _GraphedTrainStep:
 
 
 class DKT(MetaTemplate):
-    def __init__(self, model_func, n_way, n_support, kernel_type=None, amp=None, likelihood=None):
+    def __init__(self, model_func, n_way, n_support, kernel_type=None, amp=None, likelihood=None, objective=None):
         super(DKT, self).__init__(model_func, n_way, n_support)
         if likelihood is None:                                # configs.likelihood: the evaluation drivers' --likelihood (None: "gaussian")
             likelihood = configs.likelihood or "gaussian"
@@ -222,6 +239,11 @@ class DKT(MetaTemplate):
         # labels as Gaussian targets with a fixed noise per row (docs/DIRICHLET.md; up to 127 rows, any number with the linear kernels on up to 64
         # features).  Not a module, parameter or buffer: the state dict is the same
         self.likelihood_type = likelihood
+        # what the Gaussian likelihood is fitted by: "mll", the marginal likelihood (the reference), or "loo", the leave-one-out predictive likelihood of the same
+        # model (GPML 5.4.2; docs/LOO.md; up to 127 rows per episode).  train_loop and the adaptation of correct(x, N > 0) minimise it; prediction is the same
+        self.objective_type = objective_name(objective)
+        if self.objective_type == "loo" and likelihood != "gaussian":
+            raise ValueError("objective='loo' is the leave-one-out likelihood of the Gaussian model: likelihood must be 'gaussian', got %r" % (likelihood,))
         self.kernel_type = configs.kernel_type if kernel_type is None else kernel_type
         # mixed-precision backbone (opt-in): "bf16" runs the backbone under torch.autocast up to, not including, bn_out; the GP head stays fp32.
         # The fused front end takes the 16-bit trunk features as they are (libdkt_x16.so); every other route converts them once with .float().
@@ -443,6 +465,11 @@ class DKT(MetaTemplate):
                 xb, None if bn is None else bn.weight, None if bn is None else bn.bias, yt, nr, sv, mean, cw,
                 eps=1e-5 if bn is None else bn.eps, use_bn=bn is not None)
             jit = None
+        elif self.objective_type == "loo":
+            check_loo_rows(n, c)
+            obj, logp, alpha, info, jit, mu_loo, var_loo, e, bmean, bvar, a, s, rnorm = ops.episode_loss_loo_bn(
+                xb, None if bn is None else bn.weight, None if bn is None else bn.bias, y, sv, mean, noise, cw,
+                eps=1e-5 if bn is None else bn.eps, jitter0=self.jitter0, max_tries=self.max_tries, use_bn=bn is not None)
         else:
             if bn is not None:
                 outs = ops.episode_loss_bn(xb, bn.weight, bn.bias, y, sv, mean, noise, cw, eps=bn.eps, jitter0=self.jitter0,
@@ -507,6 +534,14 @@ class DKT(MetaTemplate):
             obj, logp, alpha, info, e = ops.episode_loss_dirichlet(zb, yt, nr, sv, mean, cw, self.kernel_type, self.model.lengthscale, self.model.offset,
                                                                    unit_rows=bool(self.normalize))
             return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=None, e=None if e is None else e.detach())      # (no E in feature space)
+        if self.objective_type == "loo":
+            # minimise -(1/C) sum_c loo_c / N: the same scaling and class weights as the marginal likelihood below, every kernel through E (one launch over all
+            # (episode, class) matrices)
+            check_loo_rows(n, c)
+            obj, logp, alpha, info, jit, mu_loo, var_loo, e = ops.episode_loss_loo(zb, y, sv, mean, noise, cw, self.kernel_type, self.model.lengthscale,
+                                                                                   self.model.offset, unit_rows=bool(self.normalize), jitter0=self.jitter0,
+                                                                                   max_tries=self.max_tries)
+            return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=jit, e=e.detach(), mu_loo=mu_loo, var_loo=var_loo)
         if self.kernel_type in LINEAR_KINDS:
             obj, logp, alpha, info, jit, e = ops.episode_loss_linear(zb, y, sv, mean, noise, cw, self.jitter0, self.max_tries,
                                                                      unit_rows=bool(self.normalize))
@@ -905,6 +940,32 @@ class DKT(MetaTemplate):
         eps = torch.randn(int(samples), self.n_way, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float32).to(mu.device)
         prob = ops.dirichlet_proba(mu, var, eps)[0]
         return prob if batched else prob[0]
+
+    def loo_accuracy(self, x):
+        """Leave-one-out accuracy (per cent) of the SUPPORT set of an episode x [n_way, n_support + n_query, ...]: every support row is classified by the arg-max
+        over the class models of its leave-one-out predictive mean (mu_loo of ops.loo: the row left out of the conditioning set), the first of several equal maxima.
+        One factorisation per class model, no query labels: a validation signal that costs nothing more than the objective.  The call's outputs stay in
+        `_last["loo"]`."""
+        self.n_query = x.size(1) - self.n_support
+        self._check_way(self.n_way)
+        x_support, _ = self._split(x)
+        ns = x_support.shape[0]
+        check_loo_rows(ns, self.n_way, "n_way * n_support")
+        with torch.no_grad():
+            self._mode(False)
+            zs = self._embed(x_support).detach().float().unsqueeze(0)
+            sv, mean, noise, ls, off = self._hypers_detached()
+            e = (ops.kernel_matrix(zs, None, self.kernel_type) if self.kernel_type in LINEAR_KINDS
+                 else ops.kernel_matrix_per_class(zs, None, self.kernel_type, ls, off))
+            out = ops.loo(e, self._targets(self.n_way, self.n_support, zs.device), sv, mean, noise, jitter0=self.jitter0, max_tries=self.max_tries)
+            self._last["loo"] = out
+            if int(out["info"].abs().max().item()) != 0:
+                _not_pd("DKT.loo_accuracy")
+            mu = out["mu_loo"][0]
+            cidx = torch.arange(mu.shape[0], device=mu.device).view(-1, 1)
+            labels = torch.where(mu == mu.max(0, keepdim=True).values, cidx, torch.full_like(cidx, mu.shape[0])).min(0).values
+            y_s = torch.arange(self.n_way, device=mu.device).repeat_interleave(self.n_support)
+            return float((labels == y_s).float().mean().item() * 100.0)
 
     def correct(self, x, N=0, laplace=False):
         out = self._correct_device(x, N, laplace)

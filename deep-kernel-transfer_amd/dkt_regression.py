@@ -18,12 +18,12 @@ import torch
 import torch.nn as nn
 
 from . import configs, ops
-from .dkt import amp_property, backbone_autocast, gp_head
+from .dkt import amp_property, backbone_autocast, check_loo_rows, gp_head, objective_name
 from .gp import ExactGPHypers, RBF_KINDS, SPECTRAL_KINDS
 
 
 class DKT(nn.Module):
-    def __init__(self, backbone, kernel_type=None, batch_fn=None, num_mixtures=4, ard_num_dims=2916, amp=None):
+    def __init__(self, backbone, kernel_type=None, batch_fn=None, num_mixtures=4, ard_num_dims=2916, amp=None, objective=None):
         super(DKT, self).__init__()
         self.kernel_type = configs.kernel_type if kernel_type is None else kernel_type
         if self.kernel_type not in RBF_KINDS + SPECTRAL_KINDS:
@@ -37,6 +37,8 @@ class DKT(nn.Module):
         self.max_tries = 3
         # "bf16": the backbone under torch.autocast, the features converted once to fp32 for the GP (RBF / spectral: fp32 kernels); None: configs.amp
         self.amp = configs.amp if amp is None else amp
+        # "mll": the marginal likelihood (the reference); "loo": the leave-one-out predictive likelihood of the same model (docs/LOO.md; tasks of up to 127 rows)
+        self.objective_type = objective_name(objective)
         self.get_model_likelihood_mll()
 
     def get_model_likelihood_mll(self, train_x=None, train_y=None):
@@ -74,12 +76,17 @@ class DKT(nn.Module):
 
     @gp_head
     def _loss(self, z, labels):
-        """loss = -logp / N for one task z:[N,D] or a batch [B,N,D] with labels [N] / [B,N] (mean over B)."""
+        """loss = -logp / N (objective="loo": -loo / N) for one task z:[N,D] or a batch [B,N,D] with labels [N] / [B,N] (mean over B)."""
         zb = z if z.dim() == 3 else z.unsqueeze(0)
         yb = labels.reshape(zb.shape[0], 1, zb.shape[1]).to(torch.float32)
         n = zb.shape[1]
         m = self.model
         cw = torch.full((1,), -1.0 / n, device=zb.device, dtype=torch.float32)
+        if self.objective_type == "loo":
+            check_loo_rows(n, 1, "the task")
+            obj, logp, alpha, info, jit, mu_loo, var_loo = ops.loo_objective(self._base_matrix(zb), yb, m.scale_times_variance(), m.mean, m.noise, cw,
+                                                                             self.jitter0, self.max_tries)
+            return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=jit, mu_loo=mu_loo, var_loo=var_loo)
         obj, logp, alpha, info, jit = ops.mll_objective(self._base_matrix(zb), yb, m.scale_times_variance(), m.mean, m.noise, cw,
                                                         self.jitter0, self.max_tries)
         return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=jit)

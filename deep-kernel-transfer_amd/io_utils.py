@@ -43,6 +43,8 @@ def parse_args(script, argv=None):
     parser.add_argument('--meta_batch', default=1, type=int, help='[train, this build] episodes per Adam step through the batched hot path (1 = the reference: one step per episode)')
     parser.add_argument('--likelihood', default='gaussian', choices=['gaussian', 'bernoulli', 'dirichlet'],
                         help='[this build] gaussian: regression on +-1 labels (the reference); bernoulli: the Laplace marginal likelihood of a GP classifier, episodes of up to 127 rows; dirichlet: the exact marginal likelihood of the labels as Gaussian targets with a noise per row (Milios et al. 2018), up to 127 rows (default: gaussian)')
+    parser.add_argument('--objective', default='mll', choices=['mll', 'loo'],
+                        help='[this build] what the Gaussian likelihood is fitted by -- mll: the marginal likelihood (the reference); loo: the leave-one-out predictive likelihood (GPML 5.4.2), episodes of up to 127 rows (default: mll)')
     _add_amp(parser)
     if script == 'train':
         parser.add_argument('--num_classes', default=200, type=int, help='(baseline only; kept for CLI compatibility)')
@@ -59,6 +61,7 @@ def parse_args(script, argv=None):
     else:
         raise ValueError('Unknown script')
     args = _apply_amp(parser.parse_args(argv))
+    configs.objective = None if args.objective == 'mll' else args.objective          # the default of every DKT the process builds, as --amp is
     if script == 'test':
         # the default of every DKT the process builds, as --amp is: test_uncertainty.py constructs its model without passing the flag on, and would otherwise
         # evaluate a checkpoint trained under one likelihood with the posterior of another
@@ -142,6 +145,8 @@ def checkpoint_dir_for(params, save_dir):
         d += '_bernoulli'
     elif getattr(params, 'likelihood', 'gaussian') == 'dirichlet':
         d += '_dirichlet'
+    if getattr(params, 'objective', 'mll') == 'loo':                     # (the marginal-likelihood default keeps the reference's directory name)
+        d += '_loo'
     return d
 
 

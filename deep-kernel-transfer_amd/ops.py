@@ -11,6 +11,7 @@ Autograd surface
   mll_objective(e, y, sv, mean, noise, cls_weight) -> obj[B], aux     (differentiable in e, sv, mean, noise)
   laplace_objective / dirichlet_objective and their episode_loss_* forms: the same episode under a Bernoulli (Laplace approximation) or a
   Dirichlet classification likelihood (docs/LAPLACE.md, docs/DIRICHLET.md)
+  loo_objective and its episode_loss_loo* forms: the Gaussian model fitted by its leave-one-out predictive likelihood (libdkt_loo.so; docs/LOO.md)
 which replace `-self.mll(self.model(*inputs), targets)` + `.backward()` of the reference
 (methods/DKT.py:161-163, methods/DKT_regression.py:53-56).
 """
@@ -772,6 +773,52 @@ def mll_rownoise(e: torch.Tensor, y: torch.Tensor, noise_rows: torch.Tensor, sv:
     return dict(logp=logp, alpha=alpha, info=info, chol=chol, de=de, dsv=dsv, dmean=dmean)
 
 
+# Leave-one-out predictive log likelihood (GPML 5.4.2; libdkt_loo.so, include/dkt_abi_loo.h; docs/LOO.md): the second objective of a Gaussian likelihood
+LOO_WANT_GRAD = 1
+
+
+def loo_supported(n: int, c: int) -> bool:
+    """Whether dkt_loo_f32 takes N rows and C class models per episode."""
+    return 1 <= n <= _lib.LOO_MAX_N and 1 <= c <= _lib.LOO_MAX_C
+
+
+def loo(e: torch.Tensor, y: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor, noise: torch.Tensor, want_grad: bool = False,
+        cls_weight: Optional[torch.Tensor] = None, jitter0: float = 1e-6, max_tries: int = 3) -> dict:
+    """Leave-one-out predictive log likelihood of C exact-GP models per episode, K_c = sv_c E + noise_c I (dkt_loo_f32: ONE launch, the jitter ladder of
+    `mll` inside the kernel; N <= 127, C <= 32).  e: [B,N,N] (shared by the class models) or [B,C,N,N]; y: [C,N] (every episode) or [B,C,N]; sv, mean, noise:
+    C elements.  Returns dict(loo [B,C] unweighted, alpha, mu_loo, var_loo [B,C,N] -- the leave-one-out predictive mean and variance of every row --,
+    jitter [B,C], info [B,C] int32 (0 = ok; otherwise every output of that problem is NaN), and with want_grad w = cls_weight_c sv_c d loo / d K_c
+    ([B,C,N,N], or [B,N,N] summed over the classes for a shared e), dsv, dmean, dnoise [B,C] raw, as `mll` reports its own)."""
+    per_class = e.dim() == 4
+    e = _req(e, "e", 4 if per_class else 3)
+    b_, n = e.shape[0], e.shape[-1]
+    y = _req(y, "y", y.dim() if y.dim() in (2, 3) else 2)
+    c_ = y.shape[-2]
+    if e.shape[-2] != n or y.shape[-1] != n or (per_class and e.shape[1] != c_) or (y.dim() == 3 and y.shape[0] != b_):
+        raise RuntimeError("loo: e must be [B,N,N] or [B,C,N,N] and y [C,N] or [B,C,N], got %s and %s" % (tuple(e.shape), tuple(y.shape)))
+    sv = _req(sv.reshape(-1), "sv", 1)
+    mean = _req(mean.reshape(-1), "mean", 1)
+    noise = _req(noise.reshape(-1), "noise", 1)
+    cw = None if cls_weight is None else _req(cls_weight.reshape(-1), "cls_weight", 1)
+    if not (sv.numel() == mean.numel() == noise.numel() == c_) or (cw is not None and cw.numel() != c_):
+        raise RuntimeError("loo: sv / mean / noise / cls_weight must have C=%d elements" % c_)
+    dev = e.device
+    val = torch.empty((b_, c_), device=dev, dtype=torch.float32)
+    alpha, mu, var = (torch.empty((b_, c_, n), device=dev, dtype=torch.float32) for _ in range(3))
+    jit = torch.empty((b_, c_), device=dev, dtype=torch.float32)
+    info = torch.empty((b_, c_), device=dev, dtype=torch.int32)
+    w = dsv = dmean = dnoise = None
+    if want_grad:
+        w = torch.empty((b_, c_, n, n) if per_class else (b_, n, n), device=dev, dtype=torch.float32)
+        dsv, dmean, dnoise = (torch.empty((b_, c_), device=dev, dtype=torch.float32) for _ in range(3))
+    with _timed("dkt_loo_f32"):
+        st = _lib.load_loo().dkt_loo_f32(_p(e), (c_ if per_class else 1) * n * n, n * n if per_class else 0, _p(y), c_ * n if y.dim() == 3 else 0, _p(sv), _p(mean),
+                                         _p(noise), _p(cw), b_, c_, n, float(jitter0), int(max_tries), LOO_WANT_GRAD if want_grad else 0, _p(val), _p(alpha),
+                                         _p(mu), _p(var), _p(w), _p(dsv), _p(dmean), _p(dnoise), _p(jit), _p(info), _stream())
+    _lib.check(st, "dkt_loo_f32")
+    return dict(loo=val, alpha=alpha, mu_loo=mu, var_loo=var, w=w, dsv=dsv, dmean=dmean, dnoise=dnoise, jitter=jit, info=info)
+
+
 def dirichlet_proba(mu: torch.Tensor, var: torch.Tensor, eps: torch.Tensor):
     """prob[b,q,c] = mean_s softmax_c(mu[b,c,q] + sqrt(max(var[b,c,q], 0)) eps[s,c]) (dkt_dirichlet_proba_f32): mu, var [B,C,M] the latent posterior of
     `predict` / `predict_var` (zero noise), eps [S,C] the caller's standard normals, shared by every query (common random numbers).
@@ -1298,6 +1345,22 @@ class _Gaussian:
         return (None,) + hyper_grads(gobj, cw, dsv if need_sv else None, dmean if need_mean else None, dnoise if need_noise else None, shapes) + (None, None, None)
 
 
+class _LooCV(_Gaussian):
+    """Leave-one-out predictive log likelihood of the same Gaussian model on E [B,N,N] or [B,C,N,N]: loo, W = d obj / d E and the hyper-parameter parts in ONE
+    launch (dkt_loo_f32) -> obj[b] = sum_c cls_weight[c] loo[b,c].  Outputs (loo, alpha, info, jitter, mu_loo, var_loo).  Episodes of up to 127 rows (no
+    feature-space form): behind the BN trunk front end it takes the resident form only.  `de` and `backward` are the Gaussian objective's: W and the raw
+    parts follow the conventions of dkt_mll_f32."""
+    on_features, resident_only = False, True
+
+    @staticmethod
+    def forward(e, y, sv, mean, noise, cls_weight, jitter0, max_tries):
+        with torch.no_grad():
+            out = loo(e, y, sv, mean, noise, want_grad=True, cls_weight=cls_weight, jitter0=jitter0, max_tries=max_tries)
+            obj = objective(out["loo"], cls_weight)
+        return (obj, (out["loo"], out["alpha"], out["info"], out["jitter"], out["mu_loo"], out["var_loo"]),
+                (out["w"], out["dsv"], out["dmean"], out["dnoise"], cls_weight), (sv.shape, mean.shape, noise.shape))
+
+
 class _FeatureSpaceGaussian(_Gaussian):
     """The same objective for the linear kernels in feature space (D <= 64 < N), on the rows Z and not on E:
        A = Z^T Z, P = Z^T (Y - m) (dkt_lowrank_gram_f32) -> the D x D model K'_c = sv_c A + noise_c I through dkt_mll_f32 (jitter ladder and all)
@@ -1592,6 +1655,29 @@ def episode_loss_dirichlet_bn(x, gamma, beta, ytilde, noise_rows, sv, mean, cls_
     Returns (obj [B], logp, alpha, info, E, batch_mean, batch_var_unbiased, a, s, rnorm)."""
     objv = _FeatureSpaceDirichlet if x.dim() == 3 and rownoise_lowrank_applies(x.shape[1], x.shape[2], ytilde.shape[-2], x.is_cuda) else _Dirichlet
     return _EpisodeFn.apply(_BnTrunk, objv, x, gamma, beta, eps, use_bn, ytilde, noise_rows, sv, mean, cls_weight)
+
+
+def loo_objective(e, y, sv, mean, noise, cls_weight, jitter0: float = 1e-6, max_tries: int = 3):
+    """Differentiable (in e, sv, mean, noise) leave-one-out objective of B episodes, obj[b] = sum_c cls_weight[c] loo[b,c]; arguments as `loo`.
+    Returns (obj [B], loo [B,C], alpha [B,C,N], info [B,C], jitter [B,C], mu_loo [B,C,N], var_loo [B,C,N]).  One launch, no host read-back."""
+    return _EpisodeFn.apply(_GivenE, _LooCV, e, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+
+
+def episode_loss_loo(z, y, sv, mean, noise, cls_weight, kernel: str, lengthscale=None, offset=None, unit_rows: bool = False,
+                     jitter0: float = 1e-6, max_tries: int = 3):
+    """Leave-one-out training episode(s) z [B,N,D] (N <= 127, C <= 32): K_c = sv_c * k_c(z, z) + noise_c I, every kernel of the marginal-likelihood path.
+    Always through E (no feature-space form).  Returns (obj [B], loo [B,C], alpha [B,C,N], info, jitter [B,C], mu_loo, var_loo [B,C,N], E)."""
+    z = _req(z, "z", 3)
+    if kernel in LINEAR_KINDS:
+        return _EpisodeFn.apply(_LinearGram, _LooCV, z, unit_rows, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+    cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
+    return _EpisodeFn.apply(_ClassKernel, _LooCV, z, param, cmap, power, base_kind, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+
+
+def episode_loss_loo_bn(x, gamma, beta, y, sv, mean, noise, cls_weight, eps: float = 1e-5, jitter0: float = 1e-6, max_tries: int = 3, use_bn: bool = True):
+    """x [B,N,D] trunk output BEFORE bn_out (float32, bfloat16 or float16), N <= 127.
+    Returns (obj [B], loo, alpha, info, jitter, mu_loo, var_loo, E, batch_mean, batch_var_unbiased, a, s, rnorm)."""
+    return _EpisodeFn.apply(_BnTrunk, _LooCV, x, gamma, beta, eps, use_bn, y, sv, mean, noise, cls_weight, jitter0, max_tries)
 
 
 def episode_loss_class_kernel(z, y, sv, mean, noise, cls_weight, kernel: str, lengthscale=None, offset=None,

@@ -24,7 +24,7 @@ def single_test(params, seed=0):
         params.model = 'Conv4S'
     iter_num = params.n_episode or 600
     model = dkt_amd.DKT(model_dict[params.model], n_way=params.test_n_way, n_support=params.n_shot,
-                        kernel_type=configs.kernel_type, likelihood=params.likelihood)
+                        kernel_type=configs.kernel_type, likelihood=params.likelihood, objective=params.objective)
     model = model.to(torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0'))))
     checkpoint_dir = checkpoint_dir_for(params, configs.save_dir)
     modelfile = get_assigned_file(checkpoint_dir, params.save_iter) if params.save_iter != -1 else get_best_file(checkpoint_dir)

@@ -85,7 +85,7 @@ def main(argv=None):
                                     seed=params.seed + 1000 * distributed.rank())
 
     model = dkt_amd.DKT(model_dict[params.model], n_way=params.train_n_way, n_support=params.n_shot,
-                        kernel_type=configs.kernel_type, likelihood=params.likelihood)
+                        kernel_type=configs.kernel_type, likelihood=params.likelihood, objective=params.objective)
     model.init_summary()
     model.meta_batch = max(1, getattr(params, 'meta_batch', 1))
     model = model.to(torch.device('cuda', local))
