@@ -12,6 +12,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // that selects one is compiled out, the defaults are the product.  The twins library (libdkt_twins.so: the same sources with -DDKT_TWINS, loaded by the
 // tests and the A/B tools only) reads them from the environment: dkt_env.h, over the table dkt_switches.def.
 #include "dkt_env.h"
+#include "dkt_lds_dense.h"               // dkt_jitter_rung: the one jitter ladder of every marginal-likelihood kernel
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -11,11 +11,11 @@
 // lane solves L v = w_sr * ks for its own query (v in LDS, column per lane), var = kss - |v|^2.  The five-term mixture is summed in double:
 // its coefficients are about +-2000..3500 and sum to 1, in fp32 the cancellation costs 1e-4 of the probability.
 #include "../../include/dkt_abi_gpc.h"
-#include "dkt_laplace_lds.h"
+#include "dkt_lds_dense.h"
 
 namespace {
 
-using namespace dkt_laplace;             // padded, wave_sum, stage_matrix, build_b_lower, cholesky_lower, lml_term, set_lds
+using namespace dkt_lds;                 // padded, sum_le128, stage_matrix, build_b_lower, cholesky_lower, lml_term, set_lds
 constexpr int kVecs = 8;                 // LDS vectors of the mode kernel, 128 floats each
 constexpr int kVec = 128;
 constexpr int kQT = 64;                  // query points per workgroup of the predict kernel (a lane each)
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(T) void gpc_mode_kernel(const float* __restrict__ K
             st[tid] = lml_term(sy[tid], sb[tid], acc, sd[tid]);
         }
         __syncthreads();
-        float lml = wave_sum((lane < N ? st[lane] : 0.f) + (lane + kWave < N ? st[lane + kWave] : 0.f));       // every wave gets the same bits
+        float lml = sum_le128(st, N, lane);          // every wave gets the same bits
         ++iters;
         if (lml - lml_prev < 1e-10f) break;
         lml_prev = lml;

@@ -3,16 +3,16 @@
 //
 // ONE kernel instance, 256 threads.  pass 0: a workgroup per (episode, class) problem.  K_c = scale_c K and the matrix to factor stay in LDS
 // (2 N (N|1) floats + 5 KiB of vectors: 131 KiB at N = 127), as in dkt_gpc.hip.  (I + W^1/2 K W^1/2)^-1 is formed inside the factor's own N x (N|1)
-// storage: Cholesky (strict lower triangle, the pivots apart) -> U = L^-T row by row into the UPPER triangle, which the factor leaves free -> U U^T
+// storage (the family of dkt_lds_dense.h, explained there): Cholesky (strict lower triangle, the pivots apart) -> U = L^-T row by row into the UPPER triangle, which the factor leaves free -> U U^T
 // back over the lower triangle (the diagonal apart), scaled to R = W^1/2 (.)^-1 W^1/2 on the way.  diag(K R K) goes one row product k_i^T R k_i at a
 // time, G is written straight from R, g, u.  A shared K (class stride 0) has its classes summed by pass 1 of the SAME kernel (an element per thread,
 // the classes in index order) from the per-class matrices pass 0 left in the workspace: no atomics, and the sum of a shared call is bit for bit the
 // sum of the per-class call's outputs.  Plain fp32 on the VALU; every reduction has a fixed order that depends on nothing but N.
-#include "dkt_laplace_lds.h"
+#include "dkt_lds_dense.h"
 
 namespace {
 
-using namespace dkt_laplace;             // padded, wave_sum, stage_matrix, build_b_lower, cholesky_lower, lml_term, set_lds
+using namespace dkt_lds;                 // padded, wave_sum, stage_matrix, build_b_lower, cholesky_lower, lml_term, set_lds and the factor-and-invert family
 constexpr int kT = 256;
 constexpr int kVec = 128;
 constexpr int kVecs = 10;                // sf .. sred below
@@ -27,15 +27,7 @@ __global__ __launch_bounds__(kT) void laplace_grad_kernel(const float* __restric
     const int tid = threadIdx.x;
     const int NN = N * N;
     if (pass == 1) {
-        // dK[b] = sum_c Gout[b, c], the classes in index order
-        const long e = (long)blockIdx.x * kT + tid;
-        if (e < (long)B * NN) {
-            const long b = e / NN, r = e - b * NN;
-            const float* src = Gout + b * C * (long)NN + r;
-            float acc = src[0];
-            for (int c = 1; c < C; ++c) acc += src[(long)c * NN];
-            dK[e] = acc;
-        }
+        sum_classes<kT>(Gout, dK, B, C, NN);
         return;
     }
     const int NP = padded(N);
@@ -77,38 +69,18 @@ __global__ __launch_bounds__(kT) void laplace_grad_kernel(const float* __restric
     if (tid < N) {
         const float f = sf[tid], g = sg[tid];
         st[tid] = lml_term(Yp[tid], g, f, sd[tid]);
-        sA[tid * NP + tid] = 1.f / sd[tid];                       // U_ii
+        seed_upper_diagonal(sA, sd, tid, NP);
     }
     __syncthreads();
     {
-        const float lml = wave_sum((lane < N ? st[lane] : 0.f) + (lane + kWave < N ? st[lane + kWave] : 0.f));
+        const float lml = sum_le128(st, N, lane);
         if (tid == 0) lml_o[prob] = lml;
     }
-    // U = L^-T into the upper triangle, row i of L^-1 at a time: U_ji = -(sum_{k=j}^{i-1} L_ik U_jk) / L_ii, j < i
-    // Thread j owns row j of U: it reads its own earlier writes and the rows of L, which nobody writes -- no barrier inside.  The k loop is the same for
-    // every lane (guarded, not started at the lane's own j): at a given k the lanes read sA[j * NP + k], NP words apart (odd: every bank once), where a loop
-    // from k = j would walk the diagonal, NP + 1 apart -- one bank for the whole wave at NP = 127, 63, 31.  Same terms in the same order per element.
-    if (tid < N) {
-        const int j = tid;
-        for (int i = 1; i < N; ++i) {
-            float acc = 0.f;
-            for (int k = 0; k < i; ++k)
-                if (k >= j) acc += sA[i * NP + k] * sA[j * NP + k];
-            if (j < i) sA[j * NP + i] = -acc / sd[i];
-        }
-    }
+    // U = L^-T into the upper triangle, a row per thread and no barrier inside (dkt_lds_dense.h)
+    upper_inverse_rows(sA, sd, N, NP, tid);
     __syncthreads();
-    // (I + W^1/2 K W^1/2)^-1 = U U^T over the lower triangle (L is done with), scaled to R = W^1/2 (.) W^1/2; its diagonal in sr
-    for (int idx = tid; idx < NN; idx += kT) {
-        int i = idx / N, j = idx - i * N;
-        if (j <= i) {
-            float acc = 0.f;
-            for (int k = i; k < N; ++k) acc += sA[i * NP + k] * sA[j * NP + k];
-            acc = (sw[i] * acc) * sw[j];
-            if (j == i) sr[i] = acc;
-            else sA[i * NP + j] = acc;
-        }
-    }
+    // (I + W^1/2 K W^1/2)^-1 = U U^T over the lower triangle, scaled to R = W^1/2 (.) W^1/2; its diagonal in sr
+    gram_of_upper<kT>(sA, sr, N, NP, tid, [=](int i, int j, float acc) { return (sw[i] * acc) * sw[j]; });
     __syncthreads();
     // (from here on only the lower triangle of sA is read, as R_ij = R_ji; the U above it is dead)
     // diag(K R K)_i = k_i^T R k_i, a wave per row i, lanes over the rows j of R (j and j + 64); s2 = -1/2 (K_ii - that) pi (1 - pi) (1 - 2 pi)
@@ -150,7 +122,7 @@ __global__ __launch_bounds__(kT) void laplace_grad_kernel(const float* __restric
     float dot = 0.f;
     for (int idx = tid; idx < NN; idx += kT) {
         int i = idx / N, j = idx - i * N;
-        const float r = i == j ? sr[i] : (j < i ? sA[i * NP + j] : sA[j * NP + i]);
+        const float r = sym_at(sA, sr, i, j, NP);
         const float gij = 0.5f * (sg[i] * sg[j] - r) + 0.5f * (su[i] * sg[j] + sg[i] * su[j]);
         Gp[idx] = os * gij;
         dot += gij * Kp[idx];
@@ -158,7 +130,7 @@ __global__ __launch_bounds__(kT) void laplace_grad_kernel(const float* __restric
     dot = wave_sum(dot);
     if (lane == 0) sred[wave] = dot;
     __syncthreads();
-    if (tid == 0 && dscale) dscale[prob] = wc * ((sred[0] + sred[1]) + (sred[2] + sred[3]));
+    if (tid == 0 && dscale) dscale[prob] = wc * block_sum4(sred);
 }
 
 }  // namespace

@@ -33,6 +33,7 @@ struct MllArgs {
 };
 
 constexpr float DKT_HALF_LOG_2PI = 0.91893853320467274178f;
+static_assert(DKT_HALF_LOG_2PI == dkt_lds::kHalfLog2Pi, "the two spellings of 1/2 log 2 pi round to one float");
 
 // Every path: a predicate (_serves / _applies / _supports) that mll_plan() of dkt_mll.hip consults, and a launcher that gets only what its predicate admitted.
 // Wave-per-class-matrix path on the f16 matrix pipe (dkt_mll_h2.hip): the default for N + 1 <= 128 unless the Cholesky factors or exact fp32 are requested.

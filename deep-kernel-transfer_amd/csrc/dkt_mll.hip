@@ -70,11 +70,7 @@ __global__ __launch_bounds__(256) void mll_generic_kernel(MllArgs a) {
         int fail_at = 0;
         float jit = 0.f;
         for (int attempt = 0; attempt <= a.max_tries; ++attempt) {
-            jit = 0.f;
-            if (attempt > 0) {
-                jit = a.jitter0;
-                for (int i = 1; i < attempt; ++i) jit *= 10.f;
-            }
+            jit = dkt_jitter_rung(a.jitter0, attempt);
             __syncthreads();
             // ---- form the working matrix ----
             for (int idx = tid; idx < N * N; idx += 256) {

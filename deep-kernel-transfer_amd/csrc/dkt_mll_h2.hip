@@ -399,11 +399,7 @@ void mll_h2_kernel(MllArgs a, const int wpg) {
             float jit = 0.f, lsum = 0.f, quad = 0.f, aug_unscale = 1.f;
             int msc = 0;
             for (int attempt = 0; attempt <= a.max_tries; ++attempt) {
-                jit = 0.f;
-                if (attempt > 0) {
-                    jit = a.jitter0;
-                    for (int i = 1; i < attempt; ++i) jit *= 10.f;
-                }
+                jit = dkt_jitter_rung(a.jitter0, attempt);
                 int ex;
                 (void)frexpf(fmaf(svc, emax, nzc + jit), &ex);                 // max K_ii = f 2^ex, 0.5 <= f < 1
                 msc = max(0, (ex + 1) >> 1);
@@ -828,10 +824,7 @@ void mll_h2e_kernel(MllArgs a) {
         int msc = 0;
         const brsrc Er = mk_rsrc(a.E + mat * N * N, (unsigned)(N * N * 4));
         {
-            if (attempt > 0) {
-                jit = a.jitter0;
-                for (int i = 1; i < attempt; ++i) jit *= 10.f;
-            }
+            jit = dkt_jitter_rung(a.jitter0, attempt);
             // ---- E[b] -> the tile registers (diagonal tiles first: kappa needs max E_ii) ----
             load_all_e<NT>(T, Er, N, pN, c16, g4);
             float emax = 0.f, etr = 0.f;

@@ -376,11 +376,7 @@ void mll_mfma_kernel(MllArgs a, const int wpg) {
             float jit = 0.f, lsum = 0.f, quad = 0.f;
             int msc = 0;
             for (int attempt = 0; attempt <= a.max_tries; ++attempt) {
-                jit = 0.f;
-                if (attempt > 0) {
-                    jit = a.jitter0;
-                    for (int i = 1; i < attempt; ++i) jit *= 10.f;
-                }
+                jit = dkt_jitter_rung(a.jitter0, attempt);
                 int ex;
                 (void)frexpf(fmaf(svc, emax, nzc + jit), &ex);                 // max K_ii = f 2^ex, 0.5 <= f < 1
                 msc = max(0, (ex + 1) >> 1);

@@ -75,11 +75,7 @@ __global__ __launch_bounds__(256, ((NT <= 7 && !(WANT_GRAD && WANT_CHOL)) ? DKT_
         int fail_at = 0;
         float jit = 0.f;
         for (int attempt = 0; attempt <= a.max_tries; ++attempt) {
-            jit = 0.f;
-            if (attempt > 0) {
-                jit = a.jitter0;
-                for (int i = 1; i < attempt; ++i) jit *= 10.f;
-            }
+            jit = dkt_jitter_rung(a.jitter0, attempt);
 #pragma unroll
             for (int pi = 0; pi < NT; ++pi) {
 #pragma unroll

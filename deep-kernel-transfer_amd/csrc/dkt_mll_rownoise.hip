@@ -5,23 +5,22 @@
 // TWO kernel instances, 256 threads each, plain fp32 on the VALU (the choice against the fp32 MFMA route of dkt_mll_mfma.hip: docs/DIRICHLET.md).
 // rownoise_kernel, pass 0: a workgroup per (episode, class).  ONE (N + 1) x (N|1) matrix in LDS (64 KiB + 2.5 KiB of vectors at N = 127: two workgroups
 // per CU).  Rows 0 .. N-1 hold the lower triangle of K, row N holds r = y - mean: the right-looking Cholesky sweep that turns the rows into L turns row N
-// into t = L^-1 r, the forward substitution, at no barrier of its own.  logp = -1/2 t.t - sum log L_ii - N/2 log 2 pi.  Then, as in
-// dkt_laplace_grad.hip, the inverse inside the factor's own storage: U = L^-T row by row into the upper triangle, alpha = U t, K^-1 = U U^T back over
-// the lower triangle (its diagonal apart), G = 1/2 (alpha alpha^T - K^-1) written straight from it.  No jitter ladder: a pivot that is not finite and
+// into t = L^-1 r, the forward substitution, at no barrier of its own.  logp = -1/2 t.t - sum log L_ii - N/2 log 2 pi.  Then the inverse
+// inside the factor's own storage (the family of dkt_lds_dense.h, explained there): U = L^-T row by row into the upper triangle, alpha = U t, K^-1 = U U^T
+// back over the lower triangle (its diagonal apart), G = 1/2 (alpha alpha^T - K^-1) written straight from it.  No jitter ladder: a pivot that is not finite and
 // positive ends the problem (info, NaN outputs).  A shared E (class stride 0) has its classes summed by pass 1 of the SAME kernel (an element per
 // thread, the classes in index order) from the per-class matrices pass 0 left in the workspace: no atomics, and the sum of a shared call is bit for
 // bit the sum of the per-class call's outputs.  Every reduction has a fixed order that depends on nothing but N.
 // dirichlet_proba_kernel: a group of W = 2^ceil(log2 C) lanes per query, a lane per class; max and sum over the classes by xor butterflies inside
 // the group, the samples in index order (a compensated sum).  Its passes 1 .. 3 are the feature-space calls dkt_rownoise_lowrank_* (below).
-#include "dkt_laplace_lds.h"
+#include "dkt_lds_dense.h"
 
 namespace {
 
-using namespace dkt_laplace;             // kWave, padded, wave_sum, cholesky_lower_rows, set_lds
+using namespace dkt_lds;                 // the factor-and-invert family of dkt_lds_dense.h, kWave, padded, wave_sum, kHalfLog2Pi, set_lds
 constexpr int kT = 256;
 constexpr int kVec = 128;
 constexpr int kVecs = 5;                 // sd .. sred below
-constexpr float kHalfLog2Pi = 0.918938533204672742f;
 
 inline size_t rownoise_lds_bytes(int N) { return ((size_t)(N + 1) * padded(N) + kVecs * kVec) * sizeof(float); }
 
@@ -158,43 +157,27 @@ __device__ __forceinline__ void lowrank_forward(float* lds, const float* __restr
         const float t = sA[kDP * kDPP + tid];
         st[tid] = t;
         sr[tid] = 0.5f * sc * t * t - logf(sd[tid]);
-        sA[tid * kDPP + tid] = 1.f / sd[tid];
+        seed_upper_diagonal(sA, sd, tid, kDPP);
     }
     __syncthreads();
     {
-        const float lp = wave_sum(sr[lane]);
+        const float lp = wave_sum(sr[lane]);         // (exactly kDP = 64 terms: no second half)
         if (tid == 0) logp[prob] = (lp - 0.5f * rlr - 0.5f * slog) - (float)N * kHalfLog2Pi;
     }
-    // U = L^-T into the upper triangle and t = U (L^-1 u), as in the N x N pass
+    // U = L^-T into the upper triangle, a row per thread and no barrier inside (dkt_lds_dense.h);  t = U (L^-1 u) from the finished row
+    upper_inverse_rows(sA, sd, kDP, kDPP, tid);
     if (tid < kDP) {
-        const int j = tid;
-        for (int i = 1; i < kDP; ++i) {
-            float a = 0.f;
-            for (int k = 0; k < i; ++k)
-                if (k >= j) a += sA[i * kDPP + k] * sA[j * kDPP + k];
-            if (j < i) sA[j * kDPP + i] = -a / sd[i];
-        }
-        float a = 0.f;
-        for (int i = 0; i < kDP; ++i)
-            if (i >= j) a += sA[j * kDPP + i] * st[i];
-        sa[j] = a;
-        Sp[j] = a;
+        const float a = upper_row_dot(sA, st, tid, kDP, kDPP);
+        sa[tid] = a;
+        Sp[tid] = a;
     }
     __syncthreads();
     // B^-1 = U U^T over the lower triangle, its diagonal in sr
-    for (int idx = tid; idx < kDP * kDP; idx += kT) {
-        const int i = idx / kDP, j = idx - i * kDP;
-        if (j <= i) {
-            float a = 0.f;
-            for (int k = i; k < kDP; ++k) a += sA[i * kDPP + k] * sA[j * kDPP + k];
-            if (j == i) sr[i] = a;
-            else sA[i * kDPP + j] = a;
-        }
-    }
+    gram_of_upper<kT>(sA, sr, kDP, kDPP, tid);
     __syncthreads();
     for (int idx = tid; idx < kDP * kDP; idx += kT) {
         const int i = idx / kDP, j = idx - i * kDP;
-        Sp[kDP + idx] = i == j ? sr[i] : (j < i ? sA[i * kDPP + j] : sA[j * kDPP + i]);
+        Sp[kDP + idx] = i == j ? sr[i] : (j < i ? sA[i * kDPP + j] : sA[j * kDPP + i]);          // (spelled out, not sym_at: docs/MEASUREMENTS.md R18)
     }
     // d logp / d sv = 1/2 (|t|^2 - (D - tr B^-1) / s): the trace term summed as sum_i (1 - (B^-1)_ii), every term in [0, 1) and zero on the padding
     {
@@ -222,7 +205,7 @@ __device__ __forceinline__ void lowrank_forward(float* lds, const float* __restr
     asum = wave_sum(asum);
     if (lane == 0) sred[wave] = asum;
     __syncthreads();
-    if (tid == 0 && dmean) dmean[prob] = wc * ((sred[0] + sred[1]) + (sred[2] + sred[3]));
+    if (tid == 0 && dmean) dmean[prob] = wc * block_sum4(sred);
 }
 
 // pass 2, a workgroup per (episode, chunk of kRows rows): dZ = gobj_b sum_c cw_c s_c Lambda_c^-1 (r_c t_c^T - Z Q_c), Q_c = s_c t_c t_c^T + B_c^-1, the
@@ -357,15 +340,7 @@ __global__ __launch_bounds__(kT) void rownoise_kernel(const float* __restrict__ 
     const int tid = threadIdx.x;
     const int NN = N * N;
     if (pass == 1) {
-        // dE[b] = sum_c Gout[b, c], the classes in index order
-        const long e = (long)blockIdx.x * kT + tid;
-        if (e < (long)B * NN) {
-            const long b = e / NN, r = e - b * NN;
-            const float* src = Gout + b * C * (long)NN + r;
-            float acc = src[0];
-            for (int c = 1; c < C; ++c) acc += src[(long)c * NN];
-            dE[e] = acc;
-        }
+        sum_classes<kT>(Gout, dE, B, C, NN);
         return;
     }
     const int NP = padded(N);
@@ -386,11 +361,7 @@ __global__ __launch_bounds__(kT) void rownoise_kernel(const float* __restrict__ 
     const bool grad = flags & DKT_MLL_WANT_GRAD;
     float* Gp = Gout + prob * (long)NN;
 
-    for (int idx = tid; idx < NN; idx += kT) {
-        int i = idx / N, j = idx - i * N;
-        if (j <= i) sA[i * NP + j] = sc * Ep[idx] + (i == j ? Np[i] : 0.f);
-    }
-    if (tid < N) sA[N * NP + tid] = Yp[tid] - mu;
+    stage_lower_rhs<kT>(sA, Ep, sc, [=](int i) { return Np[i]; }, [=](int i) { return Yp[i] - mu; }, N, NP, tid);
     __syncthreads();
     // the Cholesky sweep over the N + 1 rows; a bad pivot ends it for the whole workgroup
     const int bad = cholesky_lower_rows<kT, true>(sA, sd, N, N + 1, NP, tid);
@@ -421,53 +392,35 @@ __global__ __launch_bounds__(kT) void rownoise_kernel(const float* __restrict__ 
         const float t = sA[N * NP + tid];
         st[tid] = t;
         sr[tid] = -0.5f * t * t - logf(sd[tid]);
-        sA[tid * NP + tid] = 1.f / sd[tid];                       // U_ii
+        seed_upper_diagonal(sA, sd, tid, NP);
     }
     __syncthreads();
     {
-        const float lp = wave_sum((lane < N ? sr[lane] : 0.f) + (lane + kWave < N ? sr[lane + kWave] : 0.f));
+        const float lp = sum_le128(sr, N, lane);
         if (tid == 0) logp[prob] = lp - (float)N * kHalfLog2Pi;
     }
-    // U = L^-T into the upper triangle, row i of L^-1 at a time: U_ji = -(sum_{k=j}^{i-1} L_ik U_jk) / L_ii, j < i.  Thread j owns row j of U: it reads
-    // its own earlier writes and the rows of L, which nobody writes -- no barrier inside.  The k loop is the same for every lane (guarded, not started at
-    // the lane's own j): the lanes read sA[j * NP + k], NP words apart (odd: every bank once).  alpha_j = sum_{i >= j} U_ji t_i from the finished row.
+    // U = L^-T into the upper triangle, a row per thread and no barrier inside (dkt_lds_dense.h);  alpha = U t from the finished row
+    upper_inverse_rows(sA, sd, N, NP, tid);
     if (tid < N) {
-        const int j = tid;
-        for (int i = 1; i < N; ++i) {
-            float acc = 0.f;
-            for (int k = 0; k < i; ++k)
-                if (k >= j) acc += sA[i * NP + k] * sA[j * NP + k];
-            if (j < i) sA[j * NP + i] = -acc / sd[i];
-        }
-        float a = 0.f;
-        for (int i = 0; i < N; ++i)
-            if (i >= j) a += sA[j * NP + i] * st[i];
-        sa[j] = a;
-        alpha[prob * N + j] = a;
+        const float a = upper_row_dot(sA, st, tid, N, NP);
+        sa[tid] = a;
+        alpha[prob * N + tid] = a;
     }
     __syncthreads();                                              // (the read of sr above is behind this barrier too: sr is rewritten below)
     if (!grad) return;
     {
-        const float s = wave_sum((lane < N ? sa[lane] : 0.f) + (lane + kWave < N ? sa[lane + kWave] : 0.f));
+        const float s = sum_le128(sa, N, lane);
         if (tid == 0 && dmean) dmean[prob] = wc * s;
     }
-    // K^-1 = U U^T over the lower triangle (L is done with); its diagonal in sr (the diagonal of sA is U's, still read here)
-    for (int idx = tid; idx < NN; idx += kT) {
-        int i = idx / N, j = idx - i * N;
-        if (j <= i) {
-            float acc = 0.f;
-            for (int k = i; k < N; ++k) acc += sA[i * NP + k] * sA[j * NP + k];
-            if (j == i) sr[i] = acc;
-            else sA[i * NP + j] = acc;
-        }
-    }
+    // K^-1 = U U^T over the lower triangle, its diagonal in sr
+    gram_of_upper<kT>(sA, sr, N, NP, tid);
     __syncthreads();
     // G = 1/2 (alpha alpha^T - K^-1);  out = cls_weight_c sv_c G;  dsv = cls_weight_c <G, E>
     const float os = wc * sc;
     float dot = 0.f;
     for (int idx = tid; idx < NN; idx += kT) {
         int i = idx / N, j = idx - i * N;
-        const float kinv = i == j ? sr[i] : (j < i ? sA[i * NP + j] : sA[j * NP + i]);
+        const float kinv = sym_at(sA, sr, i, j, NP);
         const float gij = 0.5f * (sa[i] * sa[j] - kinv);
         Gp[idx] = os * gij;
         dot += gij * Ep[idx];
@@ -475,7 +428,7 @@ __global__ __launch_bounds__(kT) void rownoise_kernel(const float* __restrict__ 
     dot = wave_sum(dot);
     if (lane == 0) sred[wave] = dot;
     __syncthreads();
-    if (tid == 0 && dsv) dsv[prob] = wc * ((sred[0] + sred[1]) + (sred[2] + sred[3]));
+    if (tid == 0 && dsv) dsv[prob] = wc * block_sum4(sred);
 }
 
 // a lane per (query, class): W lanes per query (W a power of two >= C, the lanes c >= C idle), kT / W queries per workgroup

@@ -1,8 +1,8 @@
 // libdkt_loo.so (include/dkt_abi_loo.h; docs/LOO.md): the leave-one-out predictive log likelihood of B x C exact-GP problems
 // K = sv_c E + (noise_c + jitter) I, its N leave-one-out predictions and its gradients, in ONE launch.
 //
-// ONE kernel instance, 256 threads, plain fp32 on the VALU, the problem held in LDS as in dkt_mll_rownoise.hip: one (N + 1) x (N|1) matrix (64 KiB +
-// 4.5 KiB of vectors at N = 127: two workgroups per CU).  Rows 0 .. N-1 hold the lower triangle of K, row N holds y - mean: the right-looking
+// ONE kernel instance, 256 threads, plain fp32 on the VALU, the problem held in LDS and inverted in place by the factor-and-invert family of
+// csrc/dkt_lds_dense.h (the explanation is there): one (N + 1) x (N|1) matrix (64 KiB + 4.5 KiB of vectors at N = 127: two workgroups per CU).  Rows 0 .. N-1 hold the lower triangle of K, row N holds y - mean: the right-looking
 // Cholesky sweep turns it into t = L^-1 (y - mean).  A pivot that is not finite and positive ends the attempt for the whole workgroup, which then
 // forms K again with the next rung of the jitter ladder (0, jitter0, 10 jitter0, ...): decided per matrix, inside the kernel.  Then the inverse inside
 // the factor's own storage: U = L^-T row by row into the upper triangle, alpha = U t, A = K^-1 = U U^T over the lower triangle, mirrored into the
@@ -13,15 +13,14 @@
 // thread that owns an element of W[b] adds the classes to it in index order (its own earlier write: no atomics, no workspace, a fixed order).
 // Every reduction has a fixed order that depends on nothing but N.
 #include "../../include/dkt_abi_loo.h"
-#include "dkt_laplace_lds.h"
+#include "dkt_lds_dense.h"
 
 namespace {
 
-using namespace dkt_laplace;             // kWave, padded, wave_sum, cholesky_lower_rows, set_lds
+using namespace dkt_lds;                 // the factor-and-invert family of dkt_lds_dense.h, kWave, padded, wave_sum, kHalfLog2Pi, set_lds
 constexpr int kT = 256;
 constexpr int kVec = 128;
 constexpr int kVecs = 9;                 // sd .. sred below
-constexpr float kHalfLog2Pi = 0.918938533204672742f;
 
 inline size_t loo_lds_bytes(int N) { return ((size_t)(N + 1) * padded(N) + kVecs * kVec) * sizeof(float); }
 
@@ -76,18 +75,10 @@ __global__ __launch_bounds__(kT) void loo_kernel(LooArgs a) {
         int bad = 0;
         float jit = 0.f;
         for (int attempt = 0; attempt <= a.max_tries; ++attempt) {
-            jit = 0.f;
-            if (attempt > 0) {
-                jit = a.jitter0;
-                for (int i = 1; i < attempt; ++i) jit *= 10.f;
-            }
+            jit = dkt_jitter_rung(a.jitter0, attempt);
             __syncthreads();                       // (the reads of the attempt, or of the class, before)
             const float dg = nz + jit;
-            for (int idx = tid; idx < NN; idx += kT) {
-                int i = idx / N, j = idx - i * N;
-                if (j <= i) sA[i * NP + j] = sc * Ep[idx] + (i == j ? dg : 0.f);
-            }
-            if (tid < N) sA[N * NP + tid] = Yp[tid] - mu;
+            stage_lower_rhs<kT>(sA, Ep, sc, [=](int) { return dg; }, [=](int i) { return Yp[i] - mu; }, N, NP, tid);
             __syncthreads();
             bad = cholesky_lower_rows<kT, true>(sA, sd, N, N + 1, NP, tid);
             if (!bad) break;
@@ -127,36 +118,19 @@ __global__ __launch_bounds__(kT) void loo_kernel(LooArgs a) {
         }
         if (tid < N) {
             st[tid] = sA[N * NP + tid];
-            sA[tid * NP + tid] = 1.f / sd[tid];                       // U_ii
+            seed_upper_diagonal(sA, sd, tid, NP);
         }
         __syncthreads();
-        // U = L^-T into the upper triangle, row i of L^-1 at a time: U_ji = -(sum_{k=j}^{i-1} L_ik U_jk) / L_ii, j < i.  Thread j owns row j of U: it reads its
-        // own earlier writes and the rows of L, which nobody writes -- no barrier inside (dkt_mll_rownoise.hip).  alpha_j = sum_{i >= j} U_ji t_i.
+        // U = L^-T into the upper triangle, a row per thread and no barrier inside (dkt_lds_dense.h);  alpha = U t from the finished row
+        upper_inverse_rows(sA, sd, N, NP, tid);
         if (tid < N) {
-            const int j = tid;
-            for (int i = 1; i < N; ++i) {
-                float acc = 0.f;
-                for (int k = 0; k < i; ++k)
-                    if (k >= j) acc += sA[i * NP + k] * sA[j * NP + k];
-                if (j < i) sA[j * NP + i] = -acc / sd[i];
-            }
-            float al = 0.f;
-            for (int i = 0; i < N; ++i)
-                if (i >= j) al += sA[j * NP + i] * st[i];
-            sa[j] = al;
-            a.alpha[prob * N + j] = al;
+            const float al = upper_row_dot(sA, st, tid, N, NP);
+            sa[tid] = al;
+            a.alpha[prob * N + tid] = al;
         }
         __syncthreads();
-        // A = U U^T over the lower triangle (L is done with); its diagonal in sr (the diagonal of sA is U's, still read here)
-        for (int idx = tid; idx < NN; idx += kT) {
-            int i = idx / N, j = idx - i * N;
-            if (j <= i) {
-                float acc = 0.f;
-                for (int k = i; k < N; ++k) acc += sA[i * NP + k] * sA[j * NP + k];
-                if (j == i) sr[i] = acc;
-                else sA[i * NP + j] = acc;
-            }
-        }
+        // A = U U^T over the lower triangle, its diagonal in sr
+        gram_of_upper<kT>(sA, sr, N, NP, tid);
         __syncthreads();
         // ... mirrored into the upper triangle, the diagonal in its place: all of A, symmetric bit for bit
         for (int idx = tid; idx < NN; idx += kT) {
@@ -175,7 +149,7 @@ __global__ __launch_bounds__(kT) void loo_kernel(LooArgs a) {
         }
         __syncthreads();
         {
-            const float s = wave_sum((lane < N ? sterm[lane] : 0.f) + (lane + kWave < N ? sterm[lane + kWave] : 0.f));
+            const float s = sum_le128(sterm, N, lane);
             if (tid == 0) a.loo[prob] = s - (float)N * kHalfLog2Pi;
         }
         if (!grad) continue;
@@ -187,7 +161,7 @@ __global__ __launch_bounds__(kT) void loo_kernel(LooArgs a) {
         }
         __syncthreads();
         {
-            const float s = wave_sum((lane < N ? sv_[lane] : 0.f) + (lane + kWave < N ? sv_[lane + kWave] : 0.f));
+            const float s = sum_le128(sv_, N, lane);
             if (tid == 0) a.dmean[prob] = s;
         }
         // G = -A diag(p) A + 1/2 (alpha r^T + r alpha^T) over the lower triangle in 4 x 4 tiles;  W = cls_weight_c sv_c G,  dsv = <G, E>,  dnoise = tr G
@@ -246,8 +220,8 @@ __global__ __launch_bounds__(kT) void loo_kernel(LooArgs a) {
         }
         __syncthreads();
         if (tid == 0) {
-            a.dsv[prob] = (sred[0] + sred[1]) + (sred[2] + sred[3]);
-            a.dnoise[prob] = (sred[4] + sred[5]) + (sred[6] + sred[7]);
+            a.dsv[prob] = block_sum4(sred);
+            a.dnoise[prob] = block_sum4(sred + 4);
         }
     }
 }
