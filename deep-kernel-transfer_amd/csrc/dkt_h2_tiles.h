@@ -55,13 +55,6 @@ __device__ __forceinline__ void xtyh2(const f32x4 xa, const f32x4 ya, f32x4& ca,
     ca = xtyh1<1>(xa, ya, ca); cb = xtyh1<1>(xb, yb, cb);
     ca = xtyh1<2>(xa, ya, ca); cb = xtyh1<2>(xb, yb, cb);
 }
-__device__ __forceinline__ void xty2(const f32x4 xa, const f32x4 ya, f32x4& ca, const f32x4 xb, const f32x4 yb, f32x4& cb) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        ca = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[q], ya[q], ca, 0, 0, 0);
-        cb = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[q], yb[q], cb, 0, 0, 0);
-    }
-}
 
 // -X^T of a split tile, split again: every plane goes through the matrix pipe against -I (one non-zero term per element: exact)
 __device__ __forceinline__ f32x4 neg_transpose_h2(const f32x4 xr, const h4 negI) {

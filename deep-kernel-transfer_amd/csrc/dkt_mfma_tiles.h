@@ -48,6 +48,14 @@ __device__ __forceinline__ f32x4 xty(const f32x4 x, const f32x4 y, f32x4 c) {
     return c;
 }
 __device__ __forceinline__ f32x4 xty0(const f32x4 x, const f32x4 y) { return xty(x, y, (f32x4){0.f, 0.f, 0.f, 0.f}); }
+// two independent X^T Y chains advanced alternately: the dependent-accumulate latency of one hides behind the other
+__device__ __forceinline__ void xty2(const f32x4 xa, const f32x4 ya, f32x4& ca, const f32x4 xb, const f32x4 yb, f32x4& cb) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        ca = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[q], ya[q], ca, 0, 0, 0);
+        cb = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[q], yb[q], cb, 0, 0, 0);
+    }
+}
 
 template <int P>
 __device__ __forceinline__ float rowbcast(float v) {          // DPP row_newbcast:P -- lane P of each 16-lane row to the whole row

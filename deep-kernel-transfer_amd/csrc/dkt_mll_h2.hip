@@ -29,9 +29,12 @@
 //     d logp / d K is added in fp32 when the class contributions are summed (it used to ride on the product through a sign
 //     flip, which the rho scaling of that row no longer allows).
 //
-// Diagonal tiles, E staging, the sum over the classes in LDS and the stores are those of dkt_mll_mfma.hip, which stays in the
-// library as the exact-fp32 twin (flag DKT_MLL_FORCE_F32MFMA) and serves DKT_MLL_WANT_CHOL.
-#include "dkt_h2_tiles.h"
+// This file: the f16 arithmetic policy (ArithH2: the panel product at the scale of M_kk), the scales rho / mu2 / s3, the two kernel bodies
+// and the launcher.  Tile indexing and forming, the pending-update schedule dealt over the sweep, the head of a factorisation step and E
+// staging / loading are shared with dkt_mll_mfma.hip -- which stays in the library as the exact-fp32 twin (flag DKT_MLL_FORCE_F32MFMA) and
+// serves DKT_MLL_WANT_CHOL -- and live once in dkt_wave_mll.h.  The body of mll_h2_kernel (round preamble, phase 2, the sum over the classes
+// in LDS and the stores) still follows that of mll_mfma_kernel line by line.
+#include "dkt_wave_mll.h"
 #include <cstdlib>
 
 namespace {
@@ -42,144 +45,9 @@ using namespace dkt_mfma;
 #ifndef DKT_H2E_P2H
 #define DKT_H2E_P2H 1
 #endif
-#ifndef DKT_H2_SWEEP_PRIO
+#ifndef DKT_H2_SWEEP_PRIO     // issue priority of a sweeping wave (sweep_prio, dkt_wave_mll.h)
 #define DKT_H2_SWEEP_PRIO 1
 #endif
-#define DKT_SWEEP_PRIO(p) do { if (DKT_H2_SWEEP_PRIO) __builtin_amdgcn_s_setprio(p); } while (0)
-
-constexpr int ntt(int nt) { return nt * (nt + 1) / 2; }
-__host__ __device__ constexpr int tidx(int i, int j) { return j * (j + 1) / 2 + i; }      // i <= j
-
-constexpr int H2_MAX_WPG = 5;
-
-#ifdef DKT_MFMA_CLOCKS      // measurement build (tools/mll_phase_clocks.py): s_memtime stamps per wave into the workspace pointer
-#define DKT_CLK(i) do { __builtin_amdgcn_sched_barrier(0); clk[i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define DKT_CLK(i) do { } while (0)
-#endif
-
-template <int NT>
-struct Tiles {
-    f32x4 t[NT][NT];         // [i][j], i < j: off-diagonal slots;  [j][j]: diagonal slot
-};
-
-template <bool ER>
-struct FormCtxT {
-    static constexpr bool er = ER;   // true: the raw E tile sits in the tile's own register slot (wave-per-episode kernel); false: staged in LDS
-    const f32x4* es;         // LDS: the episode's E tiles (raw, accumulator layout), shared by the waves of the episode
-    const f32x4* ys;         // LDS: this wave's targets y_c, 16-byte groups
-    int pN, c16, g4, lane;
-    float nsv, dg, mc, rsc;  // 2^30 x: -sv / kappa, -(noise + jitter) / kappa;  mean;  2^30 rho / sqrt(kappa)
-};
-
-// Tile (I, J), I <= J, of 2^30 S = -2^30 K' in the accumulator layout, from the staged E tile.  The last block column carries the
-// augmented column -rho r_s (lanes c == pN), the last diagonal tile also its mirror row, a zero at the augmented pivot and -1 on the
-// padding diagonal.
-template <int NT, int I, int J, class F>
-__device__ __forceinline__ f32x4 form_tile(const Tiles<NT>& T, const F& f) {
-    const int pN = f.pN, c16 = f.c16, g4 = f.g4;
-    f32x4 e;
-    if constexpr (F::er) e = T.t[I][J];
-    else e = f.es[tidx(I, J) * 64 + f.lane];
-    f32x4 s;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float v = f.nsv * e[q];
-        if (I == J) v = (g4 + q == c16) ? v + f.dg : v;
-        s[q] = v;
-    }
-    if constexpr (J == NT - 1) {
-        const f32x4 yv = f.ys[4 * I + (g4 >> 2)];                             // y[16 I + 4g + q]
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const bool rok = (I < NT - 1) || (g4 + q < pN);
-            s[q] = (c16 == pN) ? (rok ? (f.mc - yv[q]) * f.rsc : 0.f) : s[q];
-        }
-        if constexpr (I == NT - 1) {
-            const float yc = reinterpret_cast<const float*>(f.ys)[16 * I + c16];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float v = s[q];
-                v = (g4 + q == pN) ? ((c16 < pN) ? (f.mc - yc) * f.rsc : 0.f) : v;   // mirror row of the augmented column; pivot N = 0
-                v = (g4 + q > pN) ? ((g4 + q == c16) ? -TWO30 : 0.f) : v;       // padding: identity
-                s[q] = v;
-            }
-        }
-    }
-    return s;
-}
-
-template <int NT, int J, class F>
-__device__ __forceinline__ void form_row0(Tiles<NT>& T, const F& f) {      // tiles (0, J), J = 0 .. NT-1
-    if constexpr (J < NT) {
-        T.t[0][J] = form_tile<NT, 0, J>(T, f);
-        form_row0<NT, J + 1>(T, f);
-    }
-}
-
-// tile row 1 of block step 0's trailing update, the freshly formed tiles as C operands: 2^30 S_1j = form(1, j) + (2^15 R_01)^T (2^15 R_0j)
-template <int NT, int J, class F>
-__device__ __forceinline__ void form_trailing_row1(Tiles<NT>& T, const F& f) {
-    if constexpr (J < NT) {
-        T.t[1][J] = xtyh(T.t[0][1], T.t[0][J], form_tile<NT, 1, J>(T, f));
-        form_trailing_row1<NT, J + 1>(T, f);
-    }
-}
-
-// Trailing updates of block step K that are NOT needed by the next sweep (tile rows i >= K + 2), u = 0 .. n_pending - 1 in (i, j) order.
-template <int NT, int K> constexpr int n_pending() { return (K >= 0 && NT - K - 2 > 0) ? (NT - K - 2) * (NT - K - 1) / 2 : 0; }
-template <int NT, int K> constexpr int pend_i(int u) { int i = K + 2; while (u >= NT - i) { u -= NT - i; ++i; } return i; }
-template <int NT, int K> constexpr int pend_j(int u) { int i = K + 2; while (u >= NT - i) { u -= NT - i; ++i; } return i + u; }
-
-// The pending updates as a stream of single MFMAs, S = 0 .. n_pend_mfma - 1: two tile updates advance alternately, three plane
-// products each.
-template <int NT, int K> constexpr int n_pend_mfma() { return 6 * ((n_pending<NT, K>() + 1) / 2); }
-
-template <int NT, int K, int S0, int S1, class F>
-__device__ __forceinline__ void pend_mfma(Tiles<NT>& T, const F& f) {
-    if constexpr (S0 < S1) {
-        constexpr int u = 2 * (S0 / 6) + (S0 & 1), w = (S0 % 6) >> 1;
-        if constexpr (u < n_pending<NT, K>()) {
-            constexpr int i = pend_i<NT, K>(u), j = pend_j<NT, K>(u);
-            if constexpr (K == 0 && w == 0) T.t[i][j] = form_tile<NT, i, j>(T, f);              // block step 0 consumes E as it goes
-            T.t[i][j] = xtyh1<w>(T.t[K][i], T.t[K][j], T.t[i][j]);
-        }
-        pend_mfma<NT, K, S0 + 1, S1>(T, f);
-    }
-}
-
-constexpr int slots_of_pivot(int p) { return 1 + (15 - p + 4) / 5; }
-constexpr int slots_before(int p) { int n = 0; for (int i = 0; i < p; ++i) n += slots_of_pivot(i); return n; }
-constexpr int SWEEP_SLOTS = slots_before(16);
-
-template <int NT, int K, int SLOT, class F>
-__device__ __forceinline__ void run_slot(Tiles<NT>& T, const F& f) {
-    constexpr int NM = n_pend_mfma<NT, K>();
-    if constexpr (NM > 0) {
-        pend_mfma<NT, K, SLOT * NM / SWEEP_SLOTS, (SLOT + 1) * NM / SWEEP_SLOTS>(T, f);
-        __builtin_amdgcn_sched_barrier(0);                    // pin the MFMA between the VALU pieces
-    }
-}
-
-template <int NT, int K, int P, int I0, int SLOT, class F>
-__device__ __forceinline__ void sweep_rows_slots(Tiles<NT>& T, const F& f, float (&x)[16], const float t) {
-    if constexpr (I0 < 16) {
-        constexpr int CNT = (16 - I0) < 5 ? (16 - I0) : 5;
-        sweep_rows_piece<P, I0, CNT>(x, t);
-        run_slot<NT, K, SLOT>(T, f);
-        sweep_rows_slots<NT, K, P, I0 + CNT, SLOT + 1>(T, f, x, t);
-    }
-}
-
-template <int NT, int K, int P, bool LAST, class F>
-__device__ __forceinline__ void sweep_interleaved(Tiles<NT>& T, const F& f, float (&x)[16], float& dv, const Lane& ln, const int pn) {
-    if constexpr (P < 16) {
-        const float t = sweep_pivot_head<P, LAST>(x, dv, ln, pn);
-        run_slot<NT, K, slots_before(P)>(T, f);
-        sweep_rows_slots<NT, K, P, P + 1, slots_before(P) + 1>(T, f, x, t);
-        sweep_interleaved<NT, K, P + 1, LAST>(T, f, x, dv, ln, pn);
-    }
-}
 
 // accumulator layout (2^30 S) -> replicated column layout (S)
 __device__ __forceinline__ void sweep_begin30(const f32x4 S, float (&x)[16], float& dv) {
@@ -188,33 +56,22 @@ __device__ __forceinline__ void sweep_begin30(const f32x4 S, float (&x)[16], flo
     dv = 1.0f;
 }
 
-struct P1Ctx {
-#ifdef DKT_MFMA_CLOCKS
-    unsigned long long* clk;
-#endif
-    f32x4* myst;
+struct P1H2 : P1Base {
     h4 negIh;
-    int lane, c16, pN;
-    int fail_at;
-    float lsum, quad;
 };
 
-// Block step K of the factorisation; x / dv hold the swept diagonal tile K on entry.
-template <int NT, int K, class F>
-__device__ __forceinline__ void phase1_step(Tiles<NT>& T, const F& f, P1Ctx& c, float (&x)[16], float& dv, const Lane& ln) {
-    if constexpr (K < NT) {
-#ifdef DKT_MFMA_CLOCKS
-        __builtin_amdgcn_sched_barrier(0); c.clk[13 + 2 * K] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0);     // sweep K done
-#endif
-        const f32x4 M = sweep_end(x, ln);
-        const bool valid = (K < NT - 1) || (c.c16 < c.pN);
-        const unsigned long long badm = __ballot(valid && !(dv > 0.f)) & 0xffffull;
-        const int first = (int)__builtin_ctzll(badm | 0x10000ull);
-        c.fail_at = (c.fail_at == 0 && badm != 0) ? 16 * K + first + 1 : c.fail_at;
-        c.lsum += (valid && ln.g0) ? __builtin_amdgcn_logf(dv) : 0.f;              // log2
-        if constexpr (K == NT - 1) c.quad = -__int_as_float(__builtin_amdgcn_readlane(__float_as_int(dv), c.pN));
-        if constexpr (F::er) T.t[K][K] = M;                     // wave-per-episode kernel: M_KK takes the (dead) diagonal slot
-        else c.myst[K * 64 + c.lane] = M;
+// scaled 2-way f16 splits on v_mfma_f32_16x16x16_f16: stored tiles of R are 2^15 R split, the accumulators hold 2^30 S
+struct ArithH2 {
+    static constexpr float PAD_DIAG = -TWO30;
+    static constexpr int NMFMA = 3;
+    static constexpr int SWEEP_PRIO = DKT_H2_SWEEP_PRIO;
+    static __device__ __forceinline__ f32x4 acc(const f32x4 x, const f32x4 y, const f32x4 c) { return xtyh(x, y, c); }
+    template <int Q>
+    static __device__ __forceinline__ f32x4 acc1(const f32x4 x, const f32x4 y, const f32x4 c) { return xtyh1<Q>(x, y, c); }
+    static __device__ __forceinline__ void sweep_begin(const f32x4 S, float (&x)[16], float& dv) { sweep_begin30(S, x, dv); }
+
+    template <int NT, int K>
+    static __device__ __forceinline__ void panel(Tiles<NT>& T, P1H2& c, const f32x4 M, const float (&)[16], const Lane&, const bool) {
         if constexpr (K + 1 < NT) {
             // the panel: R_Kj = -M_KK S_Kj = (-V_KK)^T S_Kj with V = M^T; M_KK at a scale read off its largest element (>= 1: pivots <= 1)
             float mx = fmaxf(fmaxf(fabsf(M[0]), fabsf(M[1])), fmaxf(fabsf(M[2]), fabsf(M[3])));
@@ -226,91 +83,19 @@ __device__ __forceinline__ void phase1_step(Tiles<NT>& T, const F& f, P1Ctx& c, 
 #pragma unroll
             for (int j = K + 1; j < NT; ++j)
                 T.t[K][j] = split_h2(xtyh0(nV, split_h2(T.t[K][j], TWOM15)), sig_inv);          // (sig 2^15 R_Kj) / sig -> 2^15 R_Kj, split
-            // tile row K + 1 first: the next sweep and the next panel need it
-            if constexpr (K == 0) form_trailing_row1<NT, 1>(T, f);
-            else {
-#pragma unroll
-                for (int j = K + 1; j < NT; ++j) T.t[K + 1][j] = xtyh(T.t[K][K + 1], T.t[K][j], T.t[K + 1][j]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#ifdef DKT_MFMA_CLOCKS
-            c.clk[14 + 2 * K] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0);      // panel + tile row K + 1 issued
-#endif
-            DKT_SWEEP_PRIO(DKT_H2_SWEEP_PRIO);
-            sweep_begin30(T.t[K + 1][K + 1], x, dv);
-            sweep_interleaved<NT, K, 0, K + 1 == NT - 1>(T, f, x, dv, ln, c.pN);
-            DKT_SWEEP_PRIO(0);
-            phase1_step<NT, K + 1>(T, f, c, x, dv, ln);
         }
     }
-}
-
-// E[b] tile (I, J) (raw) for the stage: E is symmetric, so element [4g+q][c] = E[16J + c][16I + 4g + q] -- one 16-byte load per
-// lane; rows / columns beyond N read as 0.
-template <int NT, int I, int J>
-__device__ __forceinline__ f32x4 load_e_tile(const brsrc Er, const int N, const int pN, const int c16, const int g4) {
-    const int row = 16 * J + c16;
-    const bool row_ok = (J < NT - 1) || (c16 < pN);
-    f32x4 e;
-    if constexpr (I < NT - 1) {
-        e = bload4(Er, row_ok ? (row * N + g4) * 4 : OOB, 16 * I * 4);
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            e[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(Er, (row_ok && g4 + q < pN) ? (row * N + g4 + q) * 4 : OOB, 16 * I * 4, 0));
-    }
-    return e;
-}
-
-template <int NT, int I, int J>
-__device__ __forceinline__ void stage_e(f32x4* es, const brsrc Er, const int N, const int pN, const int c16, const int g4, const int lane,
-                                        const int w, const int wpg) {
-    if constexpr (J < NT) {
-        if ((tidx(I, J) % wpg) == w) es[tidx(I, J) * 64 + lane] = load_e_tile<NT, I, J>(Er, N, pN, c16, g4);
-        if constexpr (I < J) stage_e<NT, I + 1, J>(es, Er, N, pN, c16, g4, lane, w, wpg);
-        else stage_e<NT, 0, J + 1>(es, Er, N, pN, c16, g4, lane, w, wpg);
-    }
-}
-
-// E[b] -> the tile registers, diagonal tiles first (wave-per-episode kernel)
-template <int NT, int J>
-__device__ __forceinline__ void load_e_diag(Tiles<NT>& T, const brsrc Er, const int N, const int pN, const int c16, const int g4) {
-    if constexpr (J < NT) {
-        T.t[J][J] = load_e_tile<NT, J, J>(Er, N, pN, c16, g4);
-        load_e_diag<NT, J + 1>(T, Er, N, pN, c16, g4);
-    }
-}
-template <int NT, int I, int J>
-__device__ __forceinline__ void load_e_off(Tiles<NT>& T, const brsrc Er, const int N, const int pN, const int c16, const int g4) {
-    if constexpr (I < NT - 1) {
-        if constexpr (J < NT) {
-            T.t[I][J] = load_e_tile<NT, I, J>(Er, N, pN, c16, g4);
-            load_e_off<NT, I, J + 1>(T, Er, N, pN, c16, g4);
-        } else {
-            load_e_off<NT, I + 1, I + 2>(T, Er, N, pN, c16, g4);
-        }
-    }
-}
-template <int NT>
-__device__ __forceinline__ void load_all_e(Tiles<NT>& T, const brsrc Er, const int N, const int pN, const int c16, const int g4) {
-    load_e_diag<NT, 0>(T, Er, N, pN, c16, g4);
-    load_e_off<NT, 0, 1>(T, Er, N, pN, c16, g4);                 // row-major over the upper triangle: the order the factorisation consumes them
-}
-
-// Episodes per workgroup: as dkt_mll_mfma.hip (two episodes = 10 waves load the SIMDs (3, 3, 2, 2) at 168 VGPRs; NT = 8: one).
-template <int NT> constexpr int h2_epw() { return NT <= 7 ? 2 : 1; }
-
-#define DKT_OPAQUE_V(x) asm volatile("" : "+v"(x))
-#define DKT_OPAQUE_S(x) asm volatile("" : "+s"(x))
+};
 
 template <int NT, bool GRAD, bool WPG5>
-__global__ __attribute__((amdgpu_flat_work_group_size(64, 64 * H2_MAX_WPG * h2_epw<NT>()), amdgpu_waves_per_eu(NT <= 7 ? 3 : 2, NT <= 7 ? 3 : 2)))
+__global__ __attribute__((amdgpu_flat_work_group_size(64, 64 * MAX_WPG * epw<NT>()), amdgpu_waves_per_eu(NT <= 7 ? 3 : 2, NT <= 7 ? 3 : 2)))
 void mll_h2_kernel(MllArgs a, const int wpg) {
+    using A = ArithH2;
     constexpr int NTT = ntt(NT);
-    constexpr int EPW = h2_epw<NT>();
+    constexpr int EPW = epw<NT>();
     __shared__ f32x4 stage_all[EPW][(GRAD && WPG5 ? 5 * ((NTT + 4) / 5) : NTT) * 64];
-    __shared__ f32x4 mst[H2_MAX_WPG * EPW][NT * 64];             // per wave: the diagonal tiles M_kk
-    __shared__ f32x4 yst[H2_MAX_WPG * EPW][NT * 4];              // per wave: the targets of its class; later alpha
+    __shared__ f32x4 mst[MAX_WPG * EPW][NT * 64];             // per wave: the diagonal tiles M_kk
+    __shared__ f32x4 yst[MAX_WPG * EPW][NT * 4];              // per wave: the targets of its class; later alpha
 
     const int tid = threadIdx.x;
     const int wall = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave in the workgroup
@@ -332,6 +117,7 @@ void mll_h2_kernel(MllArgs a, const int wpg) {
 
 #ifdef DKT_MFMA_CLOCKS
     unsigned long long clk[32] = {};
+    unsigned long long clk2[16] = {};
 #endif
     DKT_CLK(0);
     for (int round = 0; round < nrounds; ++round) {
@@ -378,6 +164,9 @@ void mll_h2_kernel(MllArgs a, const int wpg) {
             const size_t bc = (size_t)b * C + c;
             FormCtxT<false> f;
             f.es = stage; f.ys = myys;
+#ifdef DKT_MFMA_CLOCKS
+            f.clk2 = clk2;
+#endif
             f.pN = pN; f.c16 = c16; f.g4 = g4; f.lane = lane; f.mc = mc;
             // kappa = 4^m >= max_i K_ii (exact in fp32): every pivot of K / kappa is <= 1, every entry of K / kappa, of its Schur
             // complements and of R is bounded by 1.
@@ -417,9 +206,9 @@ void mll_h2_kernel(MllArgs a, const int wpg) {
                 f.dg = -(nzc + jit) * ikap * TWO30;
                 f.rsc = ldexpf(TWO30, -msc - er);
                 aug_unscale = ldexpf(1.0f, er);                                 // 1 / rho
-                form_row0<NT, 0>(T, f);
+                form_row0<A, NT, 0>(T, f);
                 // ---- phase 1: factorisation.  The sweep of tile k + 1 runs ahead, interleaved with step k's remaining updates ----
-                P1Ctx pc;
+                P1H2 pc;
                 pc.myst = myst; pc.negIh = negIh;
                 pc.lane = lane; pc.c16 = c16; pc.pN = pN;
                 pc.fail_at = 0; pc.lsum = 0.f; pc.quad = 0.f;
@@ -430,11 +219,11 @@ void mll_h2_kernel(MllArgs a, const int wpg) {
 #endif
                 {
                     float dv, x[16];
-                    DKT_SWEEP_PRIO(DKT_H2_SWEEP_PRIO);
+                    sweep_prio<A, true>();
                     sweep_begin30(T.t[0][0], x, dv);
-                    sweep_interleaved<NT, -1, 0, NT == 1>(T, f, x, dv, ln, pN);
-                    DKT_SWEEP_PRIO(0);
-                    phase1_step<NT, 0>(T, f, pc, x, dv, ln);
+                    sweep_interleaved<A, NT, -1, 0, NT == 1>(T, f, x, dv, ln, pN);
+                    sweep_prio<A, false>();
+                    phase1_step<A, NT, 0>(T, f, pc, x, dv, ln);
                 }
                 fail_at = pc.fail_at; lsum = pc.lsum; quad = pc.quad * aug_unscale * aug_unscale;
                 if (fail_at == 0) break;
@@ -713,8 +502,9 @@ void mll_h2_kernel(MllArgs a, const int wpg) {
 #ifdef DKT_MFMA_CLOCKS
     DKT_CLK(8);
     if ((tid & 63) == 0 && a.ws) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(a.ws) + ((size_t)blockIdx.x * (H2_MAX_WPG * EPW) + wall) * 48;
+        unsigned long long* o = reinterpret_cast<unsigned long long*>(a.ws) + ((size_t)blockIdx.x * (MAX_WPG * EPW) + wall) * 48;
         for (int i = 0; i < 32; ++i) o[i] = clk[i];
+        for (int i = 0; i < 16; ++i) o[32 + i] = clk2[i];
     }
 #endif
 }
@@ -854,21 +644,21 @@ void mll_h2e_kernel(MllArgs a) {
             f.dg = -(nzc + jit) * ikap * TWO30;
             f.rsc = ldexpf(TWO30, -msc - er);
             aug_unscale = ldexpf(1.0f, er);                                 // 1 / rho
-            form_row0<NT, 0>(T, f);
+            form_row0<ArithH2, NT, 0>(T, f);
             DKT_PH(0);
-            P1Ctx pc;
+            P1H2 pc;
             pc.myst = nullptr; pc.negIh = negIh;
             pc.lane = lane; pc.c16 = c16; pc.pN = pN;
             pc.fail_at = 0; pc.lsum = 0.f; pc.quad = 0.f;
 #ifdef DKT_MFMA_CLOCKS
-            unsigned long long clkdummy[32];
-            pc.clk = clkdummy;
+            unsigned long long clkdummy[32], clk2dummy[16];
+            pc.clk = clkdummy; f.clk2 = clk2dummy;
 #endif
             {
                 float dv, x[16];
                 sweep_begin30(T.t[0][0], x, dv);
-                sweep_interleaved<NT, -1, 0, NT == 1>(T, f, x, dv, ln, pN);
-                phase1_step<NT, 0>(T, f, pc, x, dv, ln);
+                sweep_interleaved<ArithH2, NT, -1, 0, NT == 1>(T, f, x, dv, ln, pN);
+                phase1_step<ArithH2, NT, 0>(T, f, pc, x, dv, ln);
             }
             fail_at = pc.fail_at; lsum = pc.lsum; quad = pc.quad * aug_unscale * aug_unscale;
         }
@@ -1296,9 +1086,9 @@ void launch_h2(const MllArgs& a, hipStream_t st) {
         }
     }
     const bool epc = (a.flags & DKT_MLL_E_PER_CLASS) != 0;                  // (NT = 8 only: one wave per workgroup, one workgroup per matrix)
-    const int rounds = (a.C + H2_MAX_WPG - 1) / H2_MAX_WPG;
+    const int rounds = (a.C + MAX_WPG - 1) / MAX_WPG;
     const int wpg = epc ? 1 : (a.C + rounds - 1) / rounds;
-    constexpr int EPW = h2_epw<NT>();
+    constexpr int EPW = epw<NT>();
     const dim3 grid(((epc ? a.B * a.C : a.B) + EPW - 1) / EPW), block(64 * wpg * EPW);
     if (g && wpg == 5) hipLaunchKernelGGL((mll_h2_kernel<NT, true, true>), grid, block, 0, st, a, wpg);
     else if (g) hipLaunchKernelGGL((mll_h2_kernel<NT, true, false>), grid, block, 0, st, a, wpg);

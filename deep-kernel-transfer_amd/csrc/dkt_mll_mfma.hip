@@ -31,198 +31,40 @@
 //
 // W[b] = sum_c cls_weight_c sv_c 0.5 (alpha alpha^T - K_c^-1) is accumulated over the classes in LDS (tile layout, the
 // waves take turns in a fixed order: deterministic) and stored ONCE, mirrored.  HBM traffic = E read + W written.
-#include "dkt_mfma_tiles.h"
+//
+// This file: the fp32 arithmetic policy (ArithF32: the panel product and the Cholesky output), the kernel body and the launcher.  Tile indexing and
+// forming, the pending-update schedule dealt over the sweep, the head of a factorisation step and E staging are shared with the f16-split successor
+// (dkt_mll_h2.hip) and live once in dkt_wave_mll.h.
+#include "dkt_wave_mll.h"
 
 namespace {
 
 using namespace dkt_mfma;
 
-#ifdef DKT_MFMA_CLOCKS      // measurement build (tools/mll_phase_clocks.py): s_memtime stamps per wave into the workspace pointer
-#define DKT_CLK(i) do { __builtin_amdgcn_sched_barrier(0); clk[i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define DKT_CLK(i) do { } while (0)
-#endif
-// Issue priority of a wave while it sweeps a diagonal tile (VALU work that competes for the shared fp32-MFMA / VALU pipe with the
-// matrix instructions of the other waves of the SIMD): s_setprio.  0 = off.  Measured: -2 % (N = 105) / -3.5 % (N = 85) at 1; 3, or the
-// whole factorisation at 1, are no different.
-#ifndef DKT_MFMA_SWEEP_PRIO
+#ifndef DKT_MFMA_SWEEP_PRIO   // issue priority of a sweeping wave (sweep_prio, dkt_wave_mll.h)
 #define DKT_MFMA_SWEEP_PRIO 1
 #endif
-#define DKT_SWEEP_PRIO(p) do { if (DKT_MFMA_SWEEP_PRIO) __builtin_amdgcn_s_setprio(p); } while (0)
 
-constexpr int ntt(int nt) { return nt * (nt + 1) / 2; }
-__host__ __device__ constexpr int tidx(int i, int j) { return j * (j + 1) / 2 + i; }      // i <= j (the order the tile loops enumerate)
-
-constexpr int MFMA_MAX_WPG = 5;
-
-template <int NT>
-struct Tiles {
-    f32x4 t[NT][NT];         // [i][j], i < j: off-diagonal slots;  [j][j]: diagonal slot
-};
-
-struct FormCtx {
-    const f32x4* es;         // LDS: the episode's E tiles (raw, accumulator layout), shared by the waves of the episode
-    const f32x4* ys;         // LDS: this wave's targets y_c, 16-byte groups
-    int pN, c16, g4, lane;
-    float nsv, dg, mc, rsc;  // -sv / kappa, -(noise + jitter) / kappa, mean, 1 / sqrt(kappa)
-#ifdef DKT_MFMA_CLOCKS
-    unsigned long long* clk2;
-#endif
-};
-
-// Tile (I, J), I <= J, of S = -K' in the accumulator layout, from the staged E tile.  The last block column carries the augmented
-// column -r (lanes c == pN), the last diagonal tile also its mirror row, a zero at the augmented pivot and -1 on the padding diagonal.
-template <int NT, int I, int J>
-__device__ __forceinline__ f32x4 form_tile(const FormCtx& f) {
-    const int pN = f.pN, c16 = f.c16, g4 = f.g4;
-    const f32x4 e = f.es[tidx(I, J) * 64 + f.lane];
-    f32x4 s;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float v = f.nsv * e[q];
-        if (I == J) v = (g4 + q == c16) ? v + f.dg : v;
-        s[q] = v;
-    }
-    if constexpr (J == NT - 1) {
-        const f32x4 yv = f.ys[4 * I + (g4 >> 2)];                             // y[16 I + 4g + q]
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const bool rok = (I < NT - 1) || (g4 + q < pN);
-            s[q] = (c16 == pN) ? (rok ? (f.mc - yv[q]) * f.rsc : 0.f) : s[q];
-        }
-        if constexpr (I == NT - 1) {
-            const float yc = reinterpret_cast<const float*>(f.ys)[16 * I + c16];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float v = s[q];
-                v = (g4 + q == pN) ? ((c16 < pN) ? (f.mc - yc) * f.rsc : 0.f) : v;   // mirror row of the augmented column; pivot N = 0
-                v = (g4 + q > pN) ? ((g4 + q == c16) ? -1.0f : 0.f) : v;        // padding: identity
-                s[q] = v;
-            }
-        }
-    }
-    return s;
-}
-
-template <int NT, int I, int J>
-__device__ __forceinline__ void form_row0(Tiles<NT>& T, const FormCtx& f) {      // tiles (0, J), J = 0 .. NT-1
-    if constexpr (J < NT) {
-        T.t[0][J] = form_tile<NT, 0, J>(f);
-        form_row0<NT, I, J + 1>(T, f);
-    }
-}
-
-// tile row 1 of block step 0's trailing update, the freshly formed tiles as C operands: S_1j = form(1, j) + R_01^T R_0j
-template <int NT, int J>
-__device__ __forceinline__ void form_trailing_row1(Tiles<NT>& T, const FormCtx& f) {
-    if constexpr (J < NT) {
-        T.t[1][J] = xty(T.t[0][1], T.t[0][J], form_tile<NT, 1, J>(f));
-        form_trailing_row1<NT, J + 1>(T, f);
-    }
-}
-
-// two independent X^T Y chains advanced alternately: the dependent-accumulate latency of one hides behind the other
-__device__ __forceinline__ void xty2(const f32x4 xa, const f32x4 ya, f32x4& ca, const f32x4 xb, const f32x4 yb, f32x4& cb) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        ca = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[q], ya[q], ca, 0, 0, 0);
-        cb = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[q], yb[q], cb, 0, 0, 0);
-    }
-}
-
-// Trailing updates of block step K that are NOT needed by the next sweep (tile rows i >= K + 2), u = 0 .. n_pending - 1 in (i, j) order.
-template <int NT, int K> constexpr int n_pending() { return (K >= 0 && NT - K - 2 > 0) ? (NT - K - 2) * (NT - K - 1) / 2 : 0; }
-template <int NT, int K> constexpr int pend_i(int u) { int i = K + 2; while (u >= NT - i) { u -= NT - i; ++i; } return i; }
-template <int NT, int K> constexpr int pend_j(int u) { int i = K + 2; while (u >= NT - i) { u -= NT - i; ++i; } return i + u; }
-
-// The pending updates as a stream of single MFMAs, S = 0 .. n_pend_mfma - 1, ordered so that neighbours belong to different tiles
-// (two tile updates advance alternately: the dependent-accumulate latency of one hides behind the other).
-template <int NT, int K> constexpr int n_pend_mfma() { return 8 * ((n_pending<NT, K>() + 1) / 2); }
-
-template <int NT, int K, int S0, int S1>
-__device__ __forceinline__ void pend_mfma(Tiles<NT>& T, const FormCtx& f) {
-    if constexpr (S0 < S1) {
-        constexpr int u = 2 * (S0 / 8) + (S0 & 1), q = (S0 % 8) >> 1;
-        if constexpr (u < n_pending<NT, K>()) {
-            constexpr int i = pend_i<NT, K>(u), j = pend_j<NT, K>(u);
-            if constexpr (K == 0 && q == 0) T.t[i][j] = form_tile<NT, i, j>(f);              // block step 0 consumes E as it goes
-            T.t[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(T.t[K][i][q], T.t[K][j][q], T.t[i][j], 0, 0, 0);
-        }
-        pend_mfma<NT, K, S0 + 1, S1>(T, f);
-    }
-}
-
-// Slots of the sweep into which the pending MFMAs are dealt: one after every pivot's scalar chain and one after every piece of
-// <= 5 row updates, i.e. about one MFMA (32 cycles of the matrix pipe) per 5-6 VALU instructions (~32 cycles of issue from one wave).
-constexpr int slots_of_pivot(int p) { return 1 + (15 - p + 4) / 5; }
-constexpr int slots_before(int p) { int n = 0; for (int i = 0; i < p; ++i) n += slots_of_pivot(i); return n; }
-constexpr int SWEEP_SLOTS = slots_before(16);
-
-template <int NT, int K, int SLOT>
-__device__ __forceinline__ void run_slot(Tiles<NT>& T, const FormCtx& f) {
-    constexpr int NM = n_pend_mfma<NT, K>();
-    if constexpr (NM > 0) {
-        pend_mfma<NT, K, SLOT * NM / SWEEP_SLOTS, (SLOT + 1) * NM / SWEEP_SLOTS>(T, f);
-        __builtin_amdgcn_sched_barrier(0);                    // pin the MFMA between the VALU pieces
-    }
-}
-
-template <int NT, int K, int P, int I0, int SLOT>
-__device__ __forceinline__ void sweep_rows_slots(Tiles<NT>& T, const FormCtx& f, float (&x)[16], const float t) {
-    if constexpr (I0 < 16) {
-        constexpr int CNT = (16 - I0) < 5 ? (16 - I0) : 5;
-        sweep_rows_piece<P, I0, CNT>(x, t);
-        run_slot<NT, K, SLOT>(T, f);
-        sweep_rows_slots<NT, K, P, I0 + CNT, SLOT + 1>(T, f, x, t);
-    }
-}
-
-// The sweep of diagonal tile K + 1 with block step K's remaining trailing updates dealt over it: their MFMAs run on the matrix
-// pipe underneath the sweep's VALU work of the same wave (K = -1: the very first tile, nothing pending).
-template <int NT, int K, int P, bool LAST>
-__device__ __forceinline__ void sweep_interleaved(Tiles<NT>& T, const FormCtx& f, float (&x)[16], float& dv, const Lane& ln, const int pn) {
-    if constexpr (P < 16) {
-        const float t = sweep_pivot_head<P, LAST>(x, dv, ln, pn);
-#ifdef DKT_MFMA_CLOCKS
-        if constexpr (K == -1) { __builtin_amdgcn_sched_barrier(0); f.clk2[P] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
-#endif
-        run_slot<NT, K, slots_before(P)>(T, f);
-        sweep_rows_slots<NT, K, P, P + 1, slots_before(P) + 1>(T, f, x, t);
-        sweep_interleaved<NT, K, P + 1, LAST>(T, f, x, dv, ln, pn);
-    }
-}
-
-template <bool CHOL>
-struct P1Ctx {
-    f32x4* myst;
+struct P1F32 : P1Base {
     float* Lmat;             // CHOL: this matrix' L[N, N]
     float lsc;               // CHOL: sqrt(kappa), L = L_s sqrt(kappa)
     f32x4 negI;
-    int lane, c16, pN, N;
-    int fail_at;
-    float lsum, quad;
-#ifdef DKT_MFMA_CLOCKS
-    unsigned long long* clk;
-#endif
+    int N;
 };
 
-// Block step K of the factorisation; x / dv hold the swept diagonal tile K on entry.
-template <int NT, int K, bool CHOL>
-__device__ __forceinline__ void phase1_step(Tiles<NT>& T, const FormCtx& f, P1Ctx<CHOL>& c, float (&x)[16], float& dv, const Lane& ln) {
-    if constexpr (K < NT) {
-#ifdef DKT_MFMA_CLOCKS
-        __builtin_amdgcn_sched_barrier(0);
-        c.clk[13 + 2 * K] = __builtin_amdgcn_s_memtime();          // sweep K done
-        __builtin_amdgcn_sched_barrier(0);
-#endif
-        const f32x4 M = sweep_end(x, ln);
-        const bool valid = (K < NT - 1) || (c.c16 < c.pN);
-        const unsigned long long badm = __ballot(valid && !(dv > 0.f)) & 0xffffull;
-        const int first = (int)__builtin_ctzll(badm | 0x10000ull);
-        c.fail_at = (c.fail_at == 0 && badm != 0) ? 16 * K + first + 1 : c.fail_at;
-        c.lsum += (valid && ln.g0) ? __builtin_amdgcn_logf(dv) : 0.f;              // log2
-        if constexpr (K == NT - 1) c.quad = -__int_as_float(__builtin_amdgcn_readlane(__float_as_int(dv), c.pN));
-        c.myst[K * 64 + c.lane] = M;
+// exact fp32 on v_mfma_f32_16x16x4_f32: tiles hold S = -(Schur complement) as they are
+template <bool CHOL>
+struct ArithF32 {
+    static constexpr float PAD_DIAG = -1.0f;
+    static constexpr int NMFMA = 4;
+    static constexpr int SWEEP_PRIO = DKT_MFMA_SWEEP_PRIO;
+    static __device__ __forceinline__ f32x4 acc(const f32x4 x, const f32x4 y, const f32x4 c) { return xty(x, y, c); }
+    template <int Q>
+    static __device__ __forceinline__ f32x4 acc1(const f32x4 x, const f32x4 y, const f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(x[Q], y[Q], c, 0, 0, 0); }
+    static __device__ __forceinline__ void sweep_begin(const f32x4 S, float (&x)[16], float& dv) { dkt_mfma::sweep_begin(S, x, dv); }
+
+    template <int NT, int K>
+    static __device__ __forceinline__ void panel(Tiles<NT>& T, P1F32& c, const f32x4 M, const float (&x)[16], const Lane& ln, const bool valid) {
         if constexpr (CHOL) {
             // L[16K + c][16K + i] = R_KK[i][c] = -x[i] (i < c), 1 / M_KK[c][c] on the diagonal, zero above it
             if (ln.g0 && valid) {
@@ -236,72 +78,21 @@ __device__ __forceinline__ void phase1_step(Tiles<NT>& T, const FormCtx& f, P1Ct
             const f32x4 nV = xty0(M, c.negI);                                        // M^T (-I) = -V_KK
 #pragma unroll
             for (int j = K + 1; j < NT; ++j) T.t[K][j] = xty0(nV, T.t[K][j]);        // panel: R_Kj
-            // tile row K + 1 first: the next sweep and the next panel need it
-            if constexpr (K == 0) form_trailing_row1<NT, 1>(T, f);
-            else {
-#pragma unroll
-                for (int j = K + 1; j < NT; ++j) T.t[K + 1][j] = xty(T.t[K][K + 1], T.t[K][j], T.t[K + 1][j]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#ifdef DKT_MFMA_CLOCKS
-            c.clk[14 + 2 * K] = __builtin_amdgcn_s_memtime();      // panel + tile row K + 1 issued
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-            DKT_SWEEP_PRIO(DKT_MFMA_SWEEP_PRIO);
-            sweep_begin(T.t[K + 1][K + 1], x, dv);
-            sweep_interleaved<NT, K, 0, K + 1 == NT - 1>(T, f, x, dv, ln, c.pN);
-            DKT_SWEEP_PRIO(0);
-            phase1_step<NT, K + 1, CHOL>(T, f, c, x, dv, ln);
         }
     }
-}
-
-// E[b] tile (I, J) (raw) for the stage: E is symmetric, so element [4g+q][c] = E[16J + c][16I + 4g + q] -- one 16-byte load per
-// lane; rows / columns beyond N read as 0.
-template <int NT, int I, int J>
-__device__ __forceinline__ f32x4 load_e_tile(const brsrc Er, const int N, const int pN, const int c16, const int g4) {
-    const int row = 16 * J + c16;
-    const bool row_ok = (J < NT - 1) || (c16 < pN);
-    f32x4 e;
-    if constexpr (I < NT - 1) {
-        e = bload4(Er, row_ok ? (row * N + g4) * 4 : OOB, 16 * I * 4);
-    } else {
-        // last diagonal tile: the four columns may run past N (and past the end of E[b]): element-wise loads
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            e[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(Er, (row_ok && g4 + q < pN) ? (row * N + g4 + q) * 4 : OOB, 16 * I * 4, 0));
-    }
-    return e;
-}
-
-template <int NT, int I, int J>
-__device__ __forceinline__ void stage_e(f32x4* es, const brsrc Er, const int N, const int pN, const int c16, const int g4, const int lane,
-                                        const int w, const int wpg) {
-    if constexpr (J < NT) {
-        if ((tidx(I, J) % wpg) == w) es[tidx(I, J) * 64 + lane] = load_e_tile<NT, I, J>(Er, N, pN, c16, g4);
-        if constexpr (I < J) stage_e<NT, I + 1, J>(es, Er, N, pN, c16, g4, lane, w, wpg);
-        else stage_e<NT, 0, J + 1>(es, Er, N, pN, c16, g4, lane, w, wpg);
-    }
-}
-
-// Episodes per workgroup.  The dispatcher deals the waves of a workgroup to the 4 SIMDs round-robin from SIMD 0, and at 3 waves per
-// SIMD (168 VGPRs) a second 5-wave workgroup no longer fits on SIMD 0: measured one resident workgroup per CU.  Two episodes = 10
-// waves per workgroup load the SIMDs (3, 3, 2, 2).  NT = 8 runs at 2 waves per SIMD (256 VGPRs): one episode per workgroup.
-template <int NT> constexpr int mfma_epw() { return NT <= 7 ? 2 : 1; }
-
-#define DKT_OPAQUE_V(x) asm volatile("" : "+v"(x))
-#define DKT_OPAQUE_S(x) asm volatile("" : "+s"(x))
+};
 
 template <int NT, bool GRAD, bool CHOL, bool WPG5>
-__global__ __attribute__((amdgpu_flat_work_group_size(64, 64 * MFMA_MAX_WPG * mfma_epw<NT>()), amdgpu_waves_per_eu(NT <= 7 ? 3 : 2, NT <= 7 ? 3 : 2)))
+__global__ __attribute__((amdgpu_flat_work_group_size(64, 64 * MAX_WPG * epw<NT>()), amdgpu_waves_per_eu(NT <= 7 ? 3 : 2, NT <= 7 ? 3 : 2)))
 void mll_mfma_kernel(MllArgs a, const int wpg) {
+    using A = ArithF32<CHOL>;
     constexpr int NTT = ntt(NT);
-    constexpr int EPW = mfma_epw<NT>();
+    constexpr int EPW = epw<NT>();
     // per episode: the E tiles (raw, shared by the class waves) -- and, once every wave is done with them, the exchange buffer of
     // the sum over the classes (5 waves x ceil(NTT / 5) tiles)
     __shared__ f32x4 stage_all[EPW][(GRAD && WPG5 ? 5 * ((NTT + 4) / 5) : NTT) * 64];
-    __shared__ f32x4 mst[MFMA_MAX_WPG * EPW][NT * 64];           // per wave: the diagonal tiles M_kk
-    __shared__ f32x4 yst[MFMA_MAX_WPG * EPW][NT * 4];            // per wave: the targets of its class
+    __shared__ f32x4 mst[MAX_WPG * EPW][NT * 64];           // per wave: the diagonal tiles M_kk
+    __shared__ f32x4 yst[MAX_WPG * EPW][NT * 4];            // per wave: the targets of its class
 
     const int tid = threadIdx.x;
     const int wall = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave in the workgroup
@@ -355,7 +146,7 @@ void mll_mfma_kernel(MllArgs a, const int wpg) {
             for (int q = 0; q < 4; ++q) negI[q] = (g4 + q == c16) ? -1.0f : 0.0f;
             const float svc = a.sv[c], mc = a.mean[c], nzc = a.noise[c];
             const size_t bc = (size_t)b * C + c;
-            FormCtx f;
+            FormCtxT<false> f;
             f.es = stage; f.ys = myys;
 #ifdef DKT_MFMA_CLOCKS
             f.clk2 = clk2;
@@ -384,9 +175,9 @@ void mll_mfma_kernel(MllArgs a, const int wpg) {
                 f.nsv = -svc * ikap;
                 f.dg = -(nzc + jit) * ikap;
                 f.rsc = ldexpf(1.0f, -msc);
-                form_row0<NT, 0, 0>(T, f);
+                form_row0<A, NT, 0>(T, f);
                 // ---- phase 1: factorisation.  The sweep of tile k + 1 runs ahead, interleaved with step k's remaining updates ----
-                P1Ctx<CHOL> pc;
+                P1F32 pc;
                 pc.myst = myst; pc.Lmat = CHOL ? a.L + bc * N * N : nullptr; pc.lsc = ldexpf(1.0f, msc); pc.negI = negI;
                 pc.lane = lane; pc.c16 = c16; pc.pN = pN; pc.N = N;
                 pc.fail_at = 0; pc.lsum = 0.f; pc.quad = 0.f;
@@ -397,11 +188,11 @@ void mll_mfma_kernel(MllArgs a, const int wpg) {
 #endif
                 {
                     float dv, x[16];
-                    DKT_SWEEP_PRIO(DKT_MFMA_SWEEP_PRIO);
-                    sweep_begin(T.t[0][0], x, dv);
-                    sweep_interleaved<NT, -1, 0, NT == 1>(T, f, x, dv, ln, pN);
-                    DKT_SWEEP_PRIO(0);
-                    phase1_step<NT, 0, CHOL>(T, f, pc, x, dv, ln);
+                    sweep_prio<A, true>();
+                    A::sweep_begin(T.t[0][0], x, dv);
+                    sweep_interleaved<A, NT, -1, 0, NT == 1>(T, f, x, dv, ln, pN);
+                    sweep_prio<A, false>();
+                    phase1_step<A, NT, 0>(T, f, pc, x, dv, ln);
                 }
                 fail_at = pc.fail_at; lsum = pc.lsum; quad = pc.quad;
                 if (fail_at == 0) break;
@@ -646,7 +437,7 @@ void mll_mfma_kernel(MllArgs a, const int wpg) {
 #ifdef DKT_MFMA_CLOCKS
     DKT_CLK(8);
     if ((tid & 63) == 0 && a.ws) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(a.ws) + ((size_t)blockIdx.x * (MFMA_MAX_WPG * EPW) + wall) * 48;
+        unsigned long long* o = reinterpret_cast<unsigned long long*>(a.ws) + ((size_t)blockIdx.x * (MAX_WPG * EPW) + wall) * 48;
         for (int i = 0; i < 32; ++i) o[i] = clk[i];
         for (int i = 0; i < 16; ++i) o[32 + i] = clk2[i];
     }
@@ -656,11 +447,10 @@ void mll_mfma_kernel(MllArgs a, const int wpg) {
 template <int NT>
 void launch_mfma(const MllArgs& a, hipStream_t st) {
     const bool g = (a.flags & DKT_MLL_WANT_GRAD) != 0, c = (a.flags & DKT_MLL_WANT_CHOL) != 0;
-    const int rounds = (a.C + MFMA_MAX_WPG - 1) / MFMA_MAX_WPG;
+    const int rounds = (a.C + MAX_WPG - 1) / MAX_WPG;
     const int wpg = (a.C + rounds - 1) / rounds;
-    constexpr int EPW = mfma_epw<NT>();
-    const int epw = EPW;
-    const dim3 grid((a.B + epw - 1) / epw), block(64 * wpg * epw);
+    constexpr int EPW = epw<NT>();
+    const dim3 grid((a.B + EPW - 1) / EPW), block(64 * wpg * EPW);
     if (g && c && wpg == 5) { hipLaunchKernelGGL((mll_mfma_kernel<NT, true, true, true>), grid, block, 0, st, a, wpg); return; }
     if (g && c) { hipLaunchKernelGGL((mll_mfma_kernel<NT, true, true, false>), grid, block, 0, st, a, wpg); return; }
     if (c) { hipLaunchKernelGGL((mll_mfma_kernel<NT, false, true, false>), grid, block, 0, st, a, wpg); return; }

@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void tiled_etile_kernel(const float* __restric
 }
 
 // Tile (i, j), i <= j, of S = -K' / kappa in the accumulator layout from the episode's E tiles; the augmented column / row, its zero
-// pivot and the identity padding as in form_tile of dkt_mll_mfma.hip.
+// pivot and the identity padding as in form_tile of dkt_wave_mll.h.
 __device__ __forceinline__ f32x4 form_from_e(const FormRt& f, const Geo& g, const int i, const int j, const f32x4 e) {
     const int NT = g.NT, N = g.N, pN = g.pN, c16 = g.c16, g4 = g.g4;
     f32x4 s;

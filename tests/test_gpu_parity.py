@@ -489,7 +489,7 @@ def test_h2_tile_primitives(cuda):
 
 
 def test_lane_primitives(cuda):
-    """The hardware idioms the MFMA marginal-likelihood kernel is built on (csrc/dkt_mll_mfma.hip): DPP row_newbcast, the
+    """The hardware idioms the MFMA marginal-likelihood kernels are built on (csrc/dkt_mfma_tiles.h; their shared skeleton is csrc/dkt_wave_mll.h): DPP row_newbcast, the
     v_permlane32/16_swap row spread, X^T Y straight from accumulator registers, and the DPP-fused FMA of the sweep."""
     import ctypes
     import dkt_amd
