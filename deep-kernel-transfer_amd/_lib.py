@@ -24,6 +24,8 @@ Adding a library: one ABI header under include/, one signature dict, one `LibSpe
 Beside the table, `EXT_LIBS`: extension libraries, product code whose sources live under csrc_ext/ (`LibSpec.src_dir`; they include the headers of csrc/) and which go
 through the same operations:
   loo    libdkt_loo.so    the leave-one-out predictive likelihood and its gradients (include/dkt_abi_loo.h; docs/LOO.md).
+And on its own (`POST_SPEC`, in neither dict), the same kind of library with the same operations:
+  post   libdkt_post.so   the joint posterior at test time: covariance, test likelihood, samples (include/dkt_abi_post.h; docs/POSTERIOR.md).
 """
 from __future__ import annotations
 
@@ -152,6 +154,15 @@ LOO_SIGNATURES = {
 }
 LOO_MAX_N, LOO_MAX_C = 127, 32      # the limits of include/dkt_abi_loo.h (DKT_ERR_SHAPE outside them)
 
+# libdkt_post.so (include/dkt_abi_post.h; tests check that this lists every function of the header): an extension library on its own, POST_SPEC below
+POST_SIGNATURES = {
+    "dkt_post_abi_version": (_c_i, []),
+    "dkt_posterior_workspace_bytes": (ctypes.c_size_t, [_c_i, _c_i, _c_i, _c_i]),
+    "dkt_posterior_f32": (_c_i, [_c_p, ctypes.c_long, ctypes.c_long] * 3 + [_c_p, ctypes.c_long] + [_c_p] * 5 + [_c_i] * 6 + [_c_f, _c_i] + [_c_p] * 11 +
+                          [ctypes.c_size_t, _c_p]),
+}
+POST_MAX_N, POST_MAX_M, POST_MAX_C = 127, 127, 32      # the limits of include/dkt_abi_post.h (DKT_ERR_SHAPE outside them)
+
 
 class LibSpec(NamedTuple):
     """What differs between the libraries; everything below takes one of these."""
@@ -194,6 +205,11 @@ EXT_LIBS = {
                    "dkt_loo_abi_version", src_dir=CSRC_EXT),
 }
 LOO_LIB_PATH = EXT_LIBS["loo"].path
+# The joint posterior at test time (docs/POSTERIOR.md): an extension library like the above, registered on its own -- in neither dict -- built by build_post() and
+# on first load.
+POST_SPEC = LibSpec(_so("post"), ["dkt_posterior.hip"], POST_SIGNATURES, "the joint posterior has no fallback.", "dkt_abi_post.h", "DKT_POST_ABI_VERSION",
+                    "dkt_post_abi_version", src_dir=CSRC_EXT)
+POST_LIB_PATH = POST_SPEC.path
 LIB_PATH, TWINS_LIB_PATH, X16_LIB_PATH, DATA_LIB_PATH, SMK_LIB_PATH, GPC_LIB_PATH, DIAG_LIB_PATH = (LIBS[k].path for k in ("hip", "twins", "x16", "data", "smk", "gpc", "diag"))
 
 _lock = threading.Lock()
@@ -354,7 +370,7 @@ def _compile_link(spec: LibSpec, target: str = None, replace=None, verbose=False
             if f.endswith(".objects.json"):
                 with open(os.path.join(OBJ_DIR, f)) as fh:
                     keep.update(json.load(fh))
-        known = {src for lib in list(LIBS.values()) + list(EXT_LIBS.values()) for src in lib.sources}
+        known = {src for lib in list(LIBS.values()) + list(EXT_LIBS.values()) + [POST_SPEC] for src in lib.sources}
         for f in os.listdir(OBJ_DIR):
             base = f[:-len(".res.json")] if f.endswith(".res.json") else f
             if base.endswith(".o") and base not in keep and any(base.startswith(src + ".") for src in known):
@@ -414,6 +430,10 @@ def build_loo(verbose: bool = False) -> str:
     return _build_if_stale(EXT_LIBS["loo"], verbose)
 
 
+def build_post(verbose: bool = False) -> str:
+    return _build_if_stale(POST_SPEC, verbose)
+
+
 def _header_version(spec: LibSpec) -> int:
     """The ABI version as the library's header under include/ declares it."""
     import re
@@ -443,6 +463,10 @@ def gpc_abi_version_of_header() -> int:
 
 def loo_abi_version_of_header() -> int:
     return _header_version(EXT_LIBS["loo"])
+
+
+def post_abi_version_of_header() -> int:
+    return _header_version(POST_SPEC)
 
 
 def device_code_objects(path: str = None) -> list:
@@ -638,6 +662,10 @@ def load_diag() -> ctypes.CDLL:
 
 def load_loo() -> ctypes.CDLL:
     return _load(EXT_LIBS["loo"])
+
+
+def load_post() -> ctypes.CDLL:
+    return _load(POST_SPEC)
 
 
 def reload_env(lib) -> None:

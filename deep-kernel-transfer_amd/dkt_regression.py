@@ -132,6 +132,49 @@ class DKT(nn.Module):
         var = ops.predict_var(ex, exx, out["chol"], sv, noise)
         return mu[0, 0], var[0, 0]
 
+    def _joint(self, z_support, y_support, z_query, **kw):
+        """ops.posterior of one task (z_support [N,D], y_support [N], z_query [M,D]) or of a batch [B,...] in one launch; (dict, batched)."""
+        m = self.model
+        batched = z_support.dim() == 3
+        zs, zq = (z if batched else z.unsqueeze(0) for z in (z_support.float(), z_query.float()))
+        if self.kernel_type in SPECTRAL_KINDS:
+            mix = (m.mixture_weights, m.mixture_means, m.mixture_scales)
+            e_ss, e_qs, e_qq = ops.smk(zs, None, *mix)[0], ops.smk(zq, zs, *mix)[0], ops.smk(zq, None, *mix)[0]
+        else:
+            e_ss, e_qs, e_qq = (ops.gram(a, b, ops.KERNEL_RBF, m.lengthscale) for a, b in ((zs, None), (zq, zs), (zq, None)))
+        y = y_support.reshape(zs.shape[0], 1, zs.shape[1]).to(torch.float32)
+        out = ops.posterior(e_ss, e_qs, e_qq, y, m.scale_times_variance(), m.mean, m.noise, jitter0=self.jitter0, max_tries=self.max_tries, **kw)
+        return out, batched
+
+    @torch.no_grad()
+    @gp_head
+    def posterior(self, z_support, y_support, z_query, with_noise=True):
+        """Condition on the support frames: the joint predictive distribution of the M query frames, (mean [M], cov [M,M]) -- of the observations
+        (with_noise) or of the latent function.  A batch of tasks [B,N,D], [B,N], [B,M,D] gives ([B,M], [B,M,M]) in one launch.  Up to 127 support and
+        127 query rows (docs/POSTERIOR.md)."""
+        out, batched = self._joint(z_support, y_support, z_query, with_noise=with_noise)
+        return (out["mu"][:, 0], out["cov"][:, 0]) if batched else (out["mu"][0, 0], out["cov"][0, 0])
+
+    @torch.no_grad()
+    @gp_head
+    def sample(self, z_support, y_support, z_query, n_samples, with_noise=False, generator=None):
+        """n_samples joint draws [S,M] ([B,S,M] for a batch) from the posterior at the query frames: of the latent function, or of observations (with_noise).
+        The standard normals come from torch.randn on the device ([B,1,S,M], `generator`)."""
+        b_ = z_query.shape[0] if z_query.dim() == 3 else 1
+        eps = torch.randn((b_, 1, int(n_samples), z_query.shape[-2]), device=z_query.device, dtype=torch.float32, generator=generator)
+        out, batched = self._joint(z_support, y_support, z_query, eps=eps, with_noise=with_noise, want_cov=False)
+        return out["samples"][:, 0] if batched else out["samples"][0, 0]
+
+    @torch.no_grad()
+    @gp_head
+    def joint_log_likelihood(self, z_support, y_support, z_query, y_query):
+        """(logp, lpd) of held-out targets y_query [M] under the posterior of observations: the joint predictive log density log N(y_q | mu, Sigma) and the
+        sum of its marginals sum_i log N(y_qi | mu_i, Sigma_ii); 0-dim, or [B] for a batch."""
+        b_ = z_query.shape[0] if z_query.dim() == 3 else 1
+        yq = y_query.reshape(b_, 1, z_query.shape[-2]).to(torch.float32)
+        out, batched = self._joint(z_support, y_support, z_query, yq=yq, with_noise=True, want_cov=False)
+        return (out["logp"][:, 0], out["lpd"][:, 0]) if batched else (out["logp"][0, 0], out["lpd"][0, 0])
+
     def test_loop(self, n_support, optimizer=None, inputs=None, targets=None):
         if inputs is None:
             inputs, targets = self.batch_fn("test")

@@ -84,9 +84,12 @@ def parse_args_regression(script, argv=None):
         parser.add_argument('--start_epoch', default=0, type=int, help='Starting epoch')
         parser.add_argument('--stop_epoch', default=100, type=int, help='Stopping epoch')
         parser.add_argument('--resume', action='store_true', help='continue from previous trained model with largest epoch')
-    elif script == 'test_regression':
+    elif script in ('test_regression', 'eval_regression'):
         parser.add_argument('--n_support', default=5, type=int, help='Number of points on trajectory to be given as support points')
         parser.add_argument('--n_test_epochs', default=10, type=int, help='How many test people?')
+        if script == 'eval_regression':      # eval_regression.py: test_regression.py's report, and the test NLL on request (docs/POSTERIOR.md)
+            parser.add_argument('--nll', action='store_true',
+                                help='also report the mean per-point joint and marginal predictive NLL of the test tasks')
     else:
         raise ValueError('Unknown script')
     args = _apply_amp(parser.parse_args(argv))

@@ -14,6 +14,8 @@ Autograd surface
   loo_objective and its episode_loss_loo* forms: the Gaussian model fitted by its leave-one-out predictive likelihood (libdkt_loo.so; docs/LOO.md)
 which replace `-self.mll(self.model(*inputs), targets)` + `.backward()` of the reference
 (methods/DKT.py:161-163, methods/DKT_regression.py:53-56).
+At test time (no autograd): predict / predict_var (mean, diagonal variance) and posterior (libdkt_post.so; docs/POSTERIOR.md): the joint posterior of the
+query rows -- full covariance, its factor, joint and marginal predictive log likelihood, function draws.
 """
 from __future__ import annotations
 
@@ -817,6 +819,65 @@ def loo(e: torch.Tensor, y: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor, 
                                          _p(mu), _p(var), _p(w), _p(dsv), _p(dmean), _p(dnoise), _p(jit), _p(info), _stream())
     _lib.check(st, "dkt_loo_f32")
     return dict(loo=val, alpha=alpha, mu_loo=mu, var_loo=var, w=w, dsv=dsv, dmean=dmean, dnoise=dnoise, jitter=jit, info=info)
+
+
+# The joint posterior at test time (GPML 2.2; libdkt_post.so, include/dkt_abi_post.h; docs/POSTERIOR.md): full covariance, test likelihood, function draws
+def posterior_supported(n: int, m: int, c: int) -> bool:
+    """Whether dkt_posterior_f32 takes N support rows, M query rows and C models per episode."""
+    return 1 <= n <= _lib.POST_MAX_N and 1 <= m <= _lib.POST_MAX_M and 1 <= c <= _lib.POST_MAX_C
+
+
+def posterior(e_ss: torch.Tensor, e_qs: torch.Tensor, e_qq: torch.Tensor, y: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor, noise: torch.Tensor,
+              yq: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None, with_noise: bool = True, want_cov: bool = True, want_chol: bool = False,
+              jitter0: float = 1e-6, max_tries: int = 3) -> dict:
+    """The joint posterior of C exact-GP models per episode at M query rows, K_c = sv_c E_ss + noise_c I (dkt_posterior_f32: ONE launch, the jitter ladder of
+    `mll` inside the kernel for K and for Sigma apart; N, M <= 127, C <= 32).  e_ss: [B,N,N], e_qs: [B,M,N] (query against support), e_qq: [B,M,M] -- each shared
+    by the class models, or with a class axis [B,C,...]; y: [C,N] (every episode) or [B,C,N]; sv, mean, noise: C elements; yq: [B,C,M] held-out targets or None;
+    eps: [B,C,S,M] standard normals or None; with_noise: the predictive covariance of observations (+ noise I) or of the latent function.
+    Returns dict(mu [B,C,M], cov [B,C,M,M] (None unless want_cov; bitwise symmetric), chol [B,C,M,M] lower factor of cov + jitter_q I (None unless want_chol),
+    logp, lpd [B,C] the joint and the marginal log predictive density of yq (None without yq), samples [B,C,S,M] = mu + chol eps (None without eps),
+    jitter_s, jitter_q [B,C], info_s, info_q [B,C] int32: info_s != 0 -- every output of that problem is NaN; info_q != 0 -- chol, logp and samples are)."""
+    shapes = [tuple(t.shape) if isinstance(t, torch.Tensor) else None for t in (e_ss, e_qs, e_qq, y)]
+    if None in shapes or len(shapes[0]) not in (3, 4) or len(shapes[1]) not in (3, 4) or len(shapes[2]) not in (3, 4) or len(shapes[3]) not in (2, 3):
+        raise RuntimeError("posterior: e_ss, e_qs, e_qq must be [B,(C,)N,N], [B,(C,)M,N], [B,(C,)M,M] and y [C,N] or [B,C,N], got %s" % (shapes,))
+    b_, n, m, c_ = shapes[0][0], shapes[0][-1], shapes[1][-2], shapes[3][-2]
+    ok = shapes[0][-2] == n and shapes[1][-1] == n and shapes[2][-2:] == (m, m) and shapes[3][-1] == n
+    ok = ok and all(s[0] == b_ and (len(s) == 3 or s[1] == c_) for s in shapes[:3]) and (len(shapes[3]) == 2 or shapes[3][0] == b_)
+    ok = ok and (yq is None or tuple(yq.shape) == (b_, c_, m)) and (eps is None or (eps.dim() == 4 and tuple(eps.shape[:2]) + (eps.shape[3],) == (b_, c_, m)))
+    ok = ok and all(isinstance(t, torch.Tensor) and t.numel() == c_ for t in (sv, mean, noise))
+    if not ok:
+        raise RuntimeError("posterior: inconsistent shapes: e_ss %s, e_qs %s, e_qq %s, y %s, yq %s, eps %s, sv / mean / noise of %s elements" % (
+            shapes[0], shapes[1], shapes[2], shapes[3], None if yq is None else tuple(yq.shape), None if eps is None else tuple(eps.shape),
+            [t.numel() if isinstance(t, torch.Tensor) else None for t in (sv, mean, noise)]))
+    if not posterior_supported(n, m, c_):
+        raise RuntimeError("posterior: N = %d support rows, M = %d query rows, C = %d models: dkt_posterior_f32 serves 1 <= N <= %d, 1 <= M <= %d, 1 <= C <= %d"
+                           % (n, m, c_, _lib.POST_MAX_N, _lib.POST_MAX_M, _lib.POST_MAX_C))
+    e_ss, e_qs, e_qq = _req(e_ss, "e_ss"), _req(e_qs, "e_qs"), _req(e_qq, "e_qq")
+    y = _req(y, "y")
+    sv, mean, noise = _req(sv.reshape(-1), "sv", 1), _req(mean.reshape(-1), "mean", 1), _req(noise.reshape(-1), "noise", 1)
+    yq = None if yq is None else _req(yq, "yq", 3)
+    s_ = 0 if eps is None else eps.shape[2]
+    eps = None if s_ == 0 else _req(eps, "eps", 4)
+    dev = e_ss.device
+    f32 = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)      # noqa: E731
+    mu = f32(b_, c_, m)
+    cov = f32(b_, c_, m, m) if want_cov else None
+    chol = f32(b_, c_, m, m) if want_chol else None
+    logp, lpd = (f32(b_, c_), f32(b_, c_)) if yq is not None else (None, None)
+    samples = f32(b_, c_, s_, m) if s_ else None
+    jit_s, jit_q = f32(b_, c_), f32(b_, c_)
+    info_s, info_q = (torch.empty((b_, c_), device=dev, dtype=torch.int32) for _ in range(2))
+    lib = _lib.load_post()
+    ws_bytes = int(lib.dkt_posterior_workspace_bytes(b_, c_, m, 1 if want_cov else 0))
+    ws = torch.empty((ws_bytes // 4,), device=dev, dtype=torch.float32) if ws_bytes else None
+    strides = lambda t, size: ((c_ if t.dim() == 4 else 1) * size, size if t.dim() == 4 else 0)      # noqa: E731
+    with _timed("dkt_posterior_f32"):
+        st = lib.dkt_posterior_f32(_p(e_ss), *strides(e_ss, n * n), _p(e_qs), *strides(e_qs, m * n), _p(e_qq), *strides(e_qq, m * m), _p(y),
+                                   c_ * n if y.dim() == 3 else 0, _p(sv), _p(mean), _p(noise), _p(yq), _p(eps), b_, c_, n, m, s_, 1 if with_noise else 0,
+                                   float(jitter0), int(max_tries), _p(mu), _p(cov), _p(chol), _p(logp), _p(lpd), _p(samples), _p(jit_s), _p(jit_q),
+                                   _p(info_s), _p(info_q), _p(ws), ws_bytes, _stream())
+    _lib.check(st, "dkt_posterior_f32")
+    return dict(mu=mu, cov=cov, chol=chol, logp=logp, lpd=lpd, samples=samples, jitter_s=jit_s, jitter_q=jit_q, info_s=info_s, info_q=info_q)
 
 
 def dirichlet_proba(mu: torch.Tensor, var: torch.Tensor, eps: torch.Tensor):
