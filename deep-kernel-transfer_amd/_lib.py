@@ -26,6 +26,8 @@ through the same operations:
   loo    libdkt_loo.so    the leave-one-out predictive likelihood and its gradients (include/dkt_abi_loo.h; docs/LOO.md).
 And on its own (`POST_SPEC`, in neither dict), the same kind of library with the same operations:
   post   libdkt_post.so   the joint posterior at test time: covariance, test likelihood, samples (include/dkt_abi_post.h; docs/POSTERIOR.md).
+  loofs  libdkt_loofs.so  (`LOOFS_SPEC`) the leave-one-out likelihood of the linear kernels in feature space: D <= 64, any number of rows (include/dkt_abi_loofs.h;
+                          docs/LOOFS.md).
 """
 from __future__ import annotations
 
@@ -164,6 +166,15 @@ POST_SIGNATURES = {
 POST_MAX_N, POST_MAX_M, POST_MAX_C = 127, 127, 32      # the limits of include/dkt_abi_post.h (DKT_ERR_SHAPE outside them)
 
 
+# libdkt_loofs.so (include/dkt_abi_loofs.h; tests check that this lists every function of the header): an extension library on its own, LOOFS_SPEC below
+LOOFS_SIGNATURES = {
+    "dkt_loofs_abi_version": (_c_i, []),
+    "dkt_loofs_workspace_bytes": (ctypes.c_size_t, [_c_i, _c_i, _c_i, _c_i]),
+    "dkt_loofs_f32": (_c_i, [_c_p, _c_p, ctypes.c_long] + [_c_p] * 4 + [_c_i, _c_i, _c_i, _c_i, _c_f, _c_i, ctypes.c_uint] + [_c_p] * 11 + [ctypes.c_size_t, _c_p]),
+}
+LOOFS_MAX_D, LOOFS_MAX_C, LOOFS_ROWS = 64, 32, 64      # DKT_LOOFS_MAX_D / _C / _ROWS of include/dkt_abi_loofs.h (DKT_ERR_SHAPE outside the first two; any N >= 1)
+
+
 class LibSpec(NamedTuple):
     """What differs between the libraries; everything below takes one of these."""
     path: str                               # the shared object
@@ -210,6 +221,10 @@ LOO_LIB_PATH = EXT_LIBS["loo"].path
 POST_SPEC = LibSpec(_so("post"), ["dkt_posterior.hip"], POST_SIGNATURES, "the joint posterior has no fallback.", "dkt_abi_post.h", "DKT_POST_ABI_VERSION",
                     "dkt_post_abi_version", src_dir=CSRC_EXT)
 POST_LIB_PATH = POST_SPEC.path
+# The leave-one-out likelihood in feature space (docs/LOOFS.md): registered the same way, built by build_loofs() and on first load.
+LOOFS_SPEC = LibSpec(_so("loofs"), ["dkt_loo_lowrank.hip"], LOOFS_SIGNATURES, "the feature-space leave-one-out objective has no fallback.", "dkt_abi_loofs.h",
+                     "DKT_LOOFS_ABI_VERSION", "dkt_loofs_abi_version", src_dir=CSRC_EXT)
+LOOFS_LIB_PATH = LOOFS_SPEC.path
 LIB_PATH, TWINS_LIB_PATH, X16_LIB_PATH, DATA_LIB_PATH, SMK_LIB_PATH, GPC_LIB_PATH, DIAG_LIB_PATH = (LIBS[k].path for k in ("hip", "twins", "x16", "data", "smk", "gpc", "diag"))
 
 _lock = threading.Lock()
@@ -370,7 +385,7 @@ def _compile_link(spec: LibSpec, target: str = None, replace=None, verbose=False
             if f.endswith(".objects.json"):
                 with open(os.path.join(OBJ_DIR, f)) as fh:
                     keep.update(json.load(fh))
-        known = {src for lib in list(LIBS.values()) + list(EXT_LIBS.values()) + [POST_SPEC] for src in lib.sources}
+        known = {src for lib in list(LIBS.values()) + list(EXT_LIBS.values()) + [POST_SPEC, LOOFS_SPEC] for src in lib.sources}
         for f in os.listdir(OBJ_DIR):
             base = f[:-len(".res.json")] if f.endswith(".res.json") else f
             if base.endswith(".o") and base not in keep and any(base.startswith(src + ".") for src in known):
@@ -434,6 +449,10 @@ def build_post(verbose: bool = False) -> str:
     return _build_if_stale(POST_SPEC, verbose)
 
 
+def build_loofs(verbose: bool = False) -> str:
+    return _build_if_stale(LOOFS_SPEC, verbose)
+
+
 def _header_version(spec: LibSpec) -> int:
     """The ABI version as the library's header under include/ declares it."""
     import re
@@ -467,6 +486,10 @@ def loo_abi_version_of_header() -> int:
 
 def post_abi_version_of_header() -> int:
     return _header_version(POST_SPEC)
+
+
+def loofs_abi_version_of_header() -> int:
+    return _header_version(LOOFS_SPEC)
 
 
 def device_code_objects(path: str = None) -> list:
@@ -666,6 +689,10 @@ def load_loo() -> ctypes.CDLL:
 
 def load_post() -> ctypes.CDLL:
     return _load(POST_SPEC)
+
+
+def load_loofs() -> ctypes.CDLL:
+    return _load(LOOFS_SPEC)
 
 
 def reload_env(lib) -> None:

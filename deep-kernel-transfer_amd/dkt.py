@@ -240,7 +240,7 @@ class DKT(MetaTemplate):
         # features).  Not a module, parameter or buffer: the state dict is the same
         self.likelihood_type = likelihood
         # what the Gaussian likelihood is fitted by: "mll", the marginal likelihood (the reference), or "loo", the leave-one-out predictive likelihood of the same
-        # model (GPML 5.4.2; docs/LOO.md; up to 127 rows per episode).  train_loop and the adaptation of correct(x, N > 0) minimise it; prediction is the same
+        # model (GPML 5.4.2; docs/LOO.md; up to 127 rows per episode, and the linear kernels with up to 64 features above 128 rows: docs/LOOFS.md).  train_loop and the adaptation of correct(x, N > 0) minimise it; prediction is the same
         self.objective_type = objective_name(objective)
         if self.objective_type == "loo" and likelihood != "gaussian":
             raise ValueError("objective='loo' is the leave-one-out likelihood of the Gaussian model: likelihood must be 'gaussian', got %r" % (likelihood,))
@@ -344,6 +344,22 @@ class DKT(MetaTemplate):
         the route: the loss, the conditioning and the fused evaluation all ask here."""
         n, d = z.shape[-2:] if shape is None else shape
         return self.kernel_type in LINEAR_KINDS and ops.rownoise_lowrank_applies(int(n), int(d), c, z.is_cuda)
+
+    def _loo_in_feature_space(self, z, c, shape=None, rows="n_way * (n_support + n_query)"):
+        """Does a leave-one-out episode on the rows z [.., N, D] (or, before they exist, of rows of shape (N, D) on the device of z) run in feature space
+        (ops.loo_lowrank: the linear kernels, D <= 64, rows on the GPU; by default above 128 rows)?  The ONE statement of the route: the losses and
+        loo_accuracy ask here.  Where it does not, the limits of the resident kernel hold (check_loo_rows), and the refusal names the route's condition."""
+        n, d = z.shape[-2:] if shape is None else shape
+        if self.kernel_type in LINEAR_KINDS and ops.loo_lowrank_applies(int(n), int(d), c, z.is_cuda):
+            return True
+        try:
+            check_loo_rows(int(n), c, rows)
+        except ValueError as exc:
+            if int(n) <= ops._lib.LOO_MAX_N:
+                raise
+            raise ValueError("%s; larger ones run in feature space: linear / cossim / bncossim with up to %d features (a multiple of 4), more than %d rows, "
+                             "on the GPU" % (exc, ops._lib.LOOFS_MAX_D, ops.FUSED_EP_MAX_N)) from None
+        return False
 
     def _dirichlet_targets(self, y):
         """(ytilde, noise_rows) of the +-1 one-vs-rest targets y (ops.dirichlet_targets), built once per target tensor of `_targets`."""
@@ -466,7 +482,7 @@ class DKT(MetaTemplate):
                 eps=1e-5 if bn is None else bn.eps, use_bn=bn is not None)
             jit = None
         elif self.objective_type == "loo":
-            check_loo_rows(n, c)
+            self._loo_in_feature_space(xb, c)             # (raises where neither the feature-space route nor the resident kernel takes the episode)
             obj, logp, alpha, info, jit, mu_loo, var_loo, e, bmean, bvar, a, s, rnorm = ops.episode_loss_loo_bn(
                 xb, None if bn is None else bn.weight, None if bn is None else bn.bias, y, sv, mean, noise, cw,
                 eps=1e-5 if bn is None else bn.eps, jitter0=self.jitter0, max_tries=self.max_tries, use_bn=bn is not None)
@@ -536,12 +552,12 @@ class DKT(MetaTemplate):
             return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=None, e=None if e is None else e.detach())      # (no E in feature space)
         if self.objective_type == "loo":
             # minimise -(1/C) sum_c loo_c / N: the same scaling and class weights as the marginal likelihood below, every kernel through E (one launch over all
-            # (episode, class) matrices)
-            check_loo_rows(n, c)
+            # (episode, class) matrices) -- or, the linear kernels above 128 rows, on the rows themselves (no E)
+            self._loo_in_feature_space(zb, c)
             obj, logp, alpha, info, jit, mu_loo, var_loo, e = ops.episode_loss_loo(zb, y, sv, mean, noise, cw, self.kernel_type, self.model.lengthscale,
                                                                                    self.model.offset, unit_rows=bool(self.normalize), jitter0=self.jitter0,
                                                                                    max_tries=self.max_tries)
-            return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=jit, e=e.detach(), mu_loo=mu_loo, var_loo=var_loo)
+            return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=jit, e=None if e is None else e.detach(), mu_loo=mu_loo, var_loo=var_loo)
         if self.kernel_type in LINEAR_KINDS:
             obj, logp, alpha, info, jit, e = ops.episode_loss_linear(zb, y, sv, mean, noise, cw, self.jitter0, self.max_tries,
                                                                      unit_rows=bool(self.normalize))
@@ -949,15 +965,17 @@ class DKT(MetaTemplate):
         self.n_query = x.size(1) - self.n_support
         self._check_way(self.n_way)
         x_support, _ = self._split(x)
-        ns = x_support.shape[0]
-        check_loo_rows(ns, self.n_way, "n_way * n_support")
         with torch.no_grad():
             self._mode(False)
             zs = self._embed(x_support).detach().float().unsqueeze(0)
             sv, mean, noise, ls, off = self._hypers_detached()
-            e = (ops.kernel_matrix(zs, None, self.kernel_type) if self.kernel_type in LINEAR_KINDS
-                 else ops.kernel_matrix_per_class(zs, None, self.kernel_type, ls, off))
-            out = ops.loo(e, self._targets(self.n_way, self.n_support, zs.device), sv, mean, noise, jitter0=self.jitter0, max_tries=self.max_tries)
+            y = self._targets(self.n_way, self.n_support, zs.device)
+            if self._loo_in_feature_space(zs, self.n_way, rows="n_way * n_support"):
+                out = ops.loo_lowrank(zs, y, sv, mean, noise, jitter0=self.jitter0, max_tries=self.max_tries)
+            else:
+                e = (ops.kernel_matrix(zs, None, self.kernel_type) if self.kernel_type in LINEAR_KINDS
+                     else ops.kernel_matrix_per_class(zs, None, self.kernel_type, ls, off))
+                out = ops.loo(e, y, sv, mean, noise, jitter0=self.jitter0, max_tries=self.max_tries)
             self._last["loo"] = out
             if int(out["info"].abs().max().item()) != 0:
                 _not_pd("DKT.loo_accuracy")

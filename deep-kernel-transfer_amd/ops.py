@@ -821,6 +821,59 @@ def loo(e: torch.Tensor, y: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor, 
     return dict(loo=val, alpha=alpha, mu_loo=mu, var_loo=var, w=w, dsv=dsv, dmean=dmean, dnoise=dnoise, jitter=jit, info=info)
 
 
+# ---- the leave-one-out likelihood in feature space (libdkt_loofs.so, include/dkt_abi_loofs.h; docs/LOOFS.md) ----
+def loo_lowrank_supported(n: int, d: int, c: int) -> bool:
+    """Shapes dkt_loofs_f32 takes: K_c = sv_c Z Z^T + noise_c I with D <= 64, D % 4 == 0, C <= 32, any number of rows (the limits of rownoise_lowrank_supported)."""
+    return n >= 1 and 1 <= d <= _lib.LOOFS_MAX_D and d % 4 == 0 and 1 <= c <= _lib.LOOFS_MAX_C
+
+
+def loo_lowrank_applies(n: int, d: int, c: int, on_gpu: bool = True) -> bool:
+    """Does a leave-one-out episode of the linear kernels run in feature space?  DKT_LOO_LOWRANK: 1 (default) = episodes of more than FUSED_EP_MAX_N = 128 rows, the
+    line `lowrank_applies` draws for the marginal likelihood (an episode of exactly 128 rows has no route: the resident kernel stops at 127; docs/LOOFS.md);
+    0 = never; force = wherever the shape is supported (tests: against the resident kernel below 128 rows).  Only for rows on the GPU."""
+    mode = os.environ.get("DKT_LOO_LOWRANK", "1")
+    if mode == "0" or not on_gpu or not loo_lowrank_supported(n, d, c):
+        return False
+    return mode == "force" or n > FUSED_EP_MAX_N
+
+
+def loo_lowrank(z: torch.Tensor, y: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor, noise: torch.Tensor, want_grad: bool = False,
+                cls_weight: Optional[torch.Tensor] = None, jitter0: float = 1e-6, max_tries: int = 3) -> dict:
+    """`loo` for the linear kernels on the rows themselves, K_c = sv_c Z Z^T + noise_c I (dkt_loofs_f32: ONE launch, the jitter ladder inside the kernel on the
+    D x D matrix Z^T Z + (noise_c + jitter) / sv_c I; D <= 64, any N: no N x N matrix exists).  z: [B,N,D]; y: [C,N] (every episode) or [B,C,N]; sv, mean, noise:
+    C elements.  Returns the dict of `loo` with dz [B,N,D] = sum_c cls_weight_c d loo_c / d Z in the place of w (None without want_grad, like dsv, dmean, dnoise)."""
+    z = _req(z, "z", 3)
+    b_, n, d = z.shape
+    y = _req(y, "y", y.dim() if y.dim() in (2, 3) else 2)
+    c_ = y.shape[-2]
+    if y.shape[-1] != n or (y.dim() == 3 and y.shape[0] != b_):
+        raise RuntimeError("loo_lowrank: z must be [B,N,D] and y [C,N] or [B,C,N], got %s and %s" % (tuple(z.shape), tuple(y.shape)))
+    sv = _req(sv.reshape(-1), "sv", 1)
+    mean = _req(mean.reshape(-1), "mean", 1)
+    noise = _req(noise.reshape(-1), "noise", 1)
+    cw = None if cls_weight is None else _req(cls_weight.reshape(-1), "cls_weight", 1)
+    if not (sv.numel() == mean.numel() == noise.numel() == c_) or (cw is not None and cw.numel() != c_):
+        raise RuntimeError("loo_lowrank: sv / mean / noise / cls_weight must have C=%d elements" % c_)
+    dev = z.device
+    val = torch.empty((b_, c_), device=dev, dtype=torch.float32)
+    alpha, mu, var = (torch.empty((b_, c_, n), device=dev, dtype=torch.float32) for _ in range(3))
+    jit = torch.empty((b_, c_), device=dev, dtype=torch.float32)
+    info = torch.empty((b_, c_), device=dev, dtype=torch.int32)
+    dz = dsv = dmean = dnoise = None
+    if want_grad:
+        dz = torch.empty_like(z)
+        dsv, dmean, dnoise = (torch.empty((b_, c_), device=dev, dtype=torch.float32) for _ in range(3))
+    lib = _lib.load_loofs()
+    ws_bytes = int(lib.dkt_loofs_workspace_bytes(b_, c_, n, d))
+    ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32) if ws_bytes else None
+    with _timed("dkt_loofs_f32"):
+        st = lib.dkt_loofs_f32(_p(z), _p(y), c_ * n if y.dim() == 3 else 0, _p(sv), _p(mean), _p(noise), _p(cw), b_, c_, n, d, float(jitter0), int(max_tries),
+                               LOO_WANT_GRAD if want_grad else 0, _p(val), _p(alpha), _p(mu), _p(var), _p(dz), _p(dsv), _p(dmean), _p(dnoise), _p(jit), _p(info),
+                               _p(ws), ws_bytes, _stream())
+    _lib.check(st, "dkt_loofs_f32")
+    return dict(loo=val, alpha=alpha, mu_loo=mu, var_loo=var, dz=dz, dsv=dsv, dmean=dmean, dnoise=dnoise, jitter=jit, info=info)
+
+
 # The joint posterior at test time (GPML 2.2; libdkt_post.so, include/dkt_abi_post.h; docs/POSTERIOR.md): full covariance, test likelihood, function draws
 def posterior_supported(n: int, m: int, c: int) -> bool:
     """Whether dkt_posterior_f32 takes N support rows, M query rows and C models per episode."""
@@ -1408,8 +1461,8 @@ class _Gaussian:
 
 class _LooCV(_Gaussian):
     """Leave-one-out predictive log likelihood of the same Gaussian model on E [B,N,N] or [B,C,N,N]: loo, W = d obj / d E and the hyper-parameter parts in ONE
-    launch (dkt_loo_f32) -> obj[b] = sum_c cls_weight[c] loo[b,c].  Outputs (loo, alpha, info, jitter, mu_loo, var_loo).  Episodes of up to 127 rows (no
-    feature-space form): behind the BN trunk front end it takes the resident form only.  `de` and `backward` are the Gaussian objective's: W and the raw
+    launch (dkt_loo_f32) -> obj[b] = sum_c cls_weight[c] loo[b,c].  Outputs (loo, alpha, info, jitter, mu_loo, var_loo).  Episodes of up to 127 rows (larger ones
+    of the linear kernels: _FeatureSpaceLooCV): behind the BN trunk front end it takes the resident form only.  `de` and `backward` are the Gaussian objective's: W and the raw
     parts follow the conventions of dkt_mll_f32."""
     on_features, resident_only = False, True
 
@@ -1420,6 +1473,28 @@ class _LooCV(_Gaussian):
             obj = objective(out["loo"], cls_weight)
         return (obj, (out["loo"], out["alpha"], out["info"], out["jitter"], out["mu_loo"], out["var_loo"]),
                 (out["w"], out["dsv"], out["dmean"], out["dnoise"], cls_weight), (sv.shape, mean.shape, noise.shape))
+
+
+class _FeatureSpaceLooCV(_LooCV):
+    """The same objective for the linear kernels in feature space (D <= 64, any N), on the rows Z and not on E: the D x D matrices Z^T Z + (noise_c + jitter) / sv_c I,
+    loo, the hyper-parameter parts and dZ = sum_c cls_weight_c d loo_c / d Z in ONE launch (dkt_loofs_f32).  Neither E nor W is ever formed: the 20-way episodes
+    of 400 / 420 rows.  `backward` is the Gaussian objective's."""
+    on_features, resident_only = True, False
+    de = None
+
+    @staticmethod
+    def forward(rows, y, sv, mean, noise, cls_weight, jitter0, max_tries):
+        z, _ = rows
+        with torch.no_grad():
+            out = loo_lowrank(z, y, sv, mean, noise, want_grad=True, cls_weight=cls_weight, jitter0=jitter0, max_tries=max_tries)
+            obj = objective(out["loo"], cls_weight)
+        return (obj, (out["loo"], out["alpha"], out["info"], out["jitter"], out["mu_loo"], out["var_loo"]),
+                (out["dz"], out["dsv"], out["dmean"], out["dnoise"], cls_weight), (sv.shape, mean.shape, noise.shape))
+
+    @staticmethod
+    def drows(z, saved, gobj):
+        dz, *_ = saved
+        return dz * gobj.reshape(-1, 1, 1)
 
 
 class _FeatureSpaceGaussian(_Gaussian):
@@ -1727,18 +1802,22 @@ def loo_objective(e, y, sv, mean, noise, cls_weight, jitter0: float = 1e-6, max_
 def episode_loss_loo(z, y, sv, mean, noise, cls_weight, kernel: str, lengthscale=None, offset=None, unit_rows: bool = False,
                      jitter0: float = 1e-6, max_tries: int = 3):
     """Leave-one-out training episode(s) z [B,N,D] (N <= 127, C <= 32): K_c = sv_c * k_c(z, z) + noise_c I, every kernel of the marginal-likelihood path.
-    Always through E (no feature-space form).  Returns (obj [B], loo [B,C], alpha [B,C,N], info, jitter [B,C], mu_loo, var_loo [B,C,N], E)."""
+    The linear kernels with D <= 64 take any N above 128 rows (loo_lowrank_applies): the episode runs in feature space and E is None.
+    Returns (obj [B], loo [B,C], alpha [B,C,N], info, jitter [B,C], mu_loo, var_loo [B,C,N], E)."""
     z = _req(z, "z", 3)
     if kernel in LINEAR_KINDS:
-        return _EpisodeFn.apply(_LinearGram, _LooCV, z, unit_rows, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+        objv = _FeatureSpaceLooCV if loo_lowrank_applies(z.shape[1], z.shape[2], y.shape[-2], z.is_cuda) else _LooCV
+        return _EpisodeFn.apply(_LinearGram, objv, z, unit_rows, y, sv, mean, noise, cls_weight, jitter0, max_tries)
     cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
     return _EpisodeFn.apply(_ClassKernel, _LooCV, z, param, cmap, power, base_kind, y, sv, mean, noise, cls_weight, jitter0, max_tries)
 
 
 def episode_loss_loo_bn(x, gamma, beta, y, sv, mean, noise, cls_weight, eps: float = 1e-5, jitter0: float = 1e-6, max_tries: int = 3, use_bn: bool = True):
-    """x [B,N,D] trunk output BEFORE bn_out (float32, bfloat16 or float16), N <= 127.
+    """x [B,N,D] trunk output BEFORE bn_out (float32, bfloat16 or float16), N <= 127 -- or, with D <= 64, any N above 128 rows: the episode runs in
+    feature space (loo_lowrank_applies) and E is None.
     Returns (obj [B], loo, alpha, info, jitter, mu_loo, var_loo, E, batch_mean, batch_var_unbiased, a, s, rnorm)."""
-    return _EpisodeFn.apply(_BnTrunk, _LooCV, x, gamma, beta, eps, use_bn, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+    objv = _FeatureSpaceLooCV if x.dim() == 3 and loo_lowrank_applies(x.shape[1], x.shape[2], y.shape[-2], x.is_cuda) else _LooCV
+    return _EpisodeFn.apply(_BnTrunk, objv, x, gamma, beta, eps, use_bn, y, sv, mean, noise, cls_weight, jitter0, max_tries)
 
 
 def episode_loss_class_kernel(z, y, sv, mean, noise, cls_weight, kernel: str, lengthscale=None, offset=None,
