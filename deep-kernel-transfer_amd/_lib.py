@@ -1,33 +1,30 @@
 """Build + ctypes binding of the project's HIP shared objects: one `LibSpec` per library in the table `LIBS`, and ONE implementation of each operation
-(staleness check, build-if-stale, header-version reader, load) that takes a spec.  The per-library names (`load_x16()`, `build_smk()`, `X16_LIB_PATH`, ...) are
-one-line views of the table.
+(staleness check, build-if-stale, header-version reader, load) that takes a key of the table: `build_lib`, `load_lib`, `header_version` (over `_build_if_stale`, `_load`, `_header_version`, which take the spec).  The per-library names
+(`load_x16()`, `build_post()`, `X16_LIB_PATH`, ...) are one-line views of the table, kept where a caller wants them.
 
 There is NO CPU fallback: every entry point of `ops` goes through these libraries, and loading raises if a shared object is missing, lacks a symbol of its
 header or implements another ABI version than the header declares.
 
-Seven in-tree shared objects, all hipcc --offload-arch=gfx950:
-  hip    libdkt_hip.so    the PRODUCT (include/dkt_abi.h): the default kernel of every call, no measurement switch, no variant instantiation;
-  x16    libdkt_x16.so    product code: the front-end calls for 16-bit (bf16 / f16) trunk features (include/dkt_abi_x16.h); apart so that the product ABI stays as it is;
-  data   libdkt_data.so   product code: the episode image transform of the image-dataset loader (include/dkt_abi_data.h); apart for the same reason;
-  smk    libdkt_smk.so    product code: the task-resident spectral-mixture kernels of the sine-wave experiment (include/dkt_abi_smk.h); apart for the same reason;
-  gpc    libdkt_gpc.so    product code: Laplace-approximation GP classification at test time, Newton mode finding and prediction (include/dkt_abi_gpc.h); apart for
-                          the same reason;
+The libraries, all hipcc --offload-arch=gfx950 (sources under csrc/; `LibSpec.src_dir` marks an extension library, whose sources live under csrc_ext/ and
+include the headers of csrc/ and of their own directory):
+  hip    libdkt_hip.so    the PRODUCT (include/dkt_abi.h): the default kernel of every call, no measurement switch, no variant instantiation; held at 250 kernels;
+  x16    libdkt_x16.so    the front-end calls for 16-bit (bf16 / f16) trunk features (include/dkt_abi_x16.h); apart so that the product ABI stays as it is;
+  data   libdkt_data.so   the episode image transform of the image-dataset loader (include/dkt_abi_data.h);
+  smk    libdkt_smk.so    the task-resident spectral-mixture kernels of the sine-wave experiment (include/dkt_abi_smk.h);
+  gpc    libdkt_gpc.so    Laplace-approximation GP classification at test time, Newton mode finding and prediction (include/dkt_abi_gpc.h);
+  loo    libdkt_loo.so    csrc_ext/: the leave-one-out predictive likelihood and its gradients (include/dkt_abi_loo.h; docs/LOO.md);
+  post   libdkt_post.so   csrc_ext/: the joint posterior at test time: covariance, test likelihood, samples (include/dkt_abi_post.h; docs/POSTERIOR.md);
+  loofs  libdkt_loofs.so  csrc_ext/: the leave-one-out likelihood of the linear kernels in feature space (include/dkt_abi_loofs.h; docs/LOOFS.md);
+  diag   libdkt_diag.so   measurement-only kernels (stream ceilings, co-residency spinners, the round-1 register-sweep kernel): no header, no version;
   twins  libdkt_twins.so  the product's sources with -DDKT_TWINS: every pipeline variant and validation twin the defaults were chosen from, selected by the
-                          environment switches of DESIGN.md's appendix.  Same ABI.  Tests and A/B tools only (DKT_TWINS=1 + a variant switch);
-  diag   libdkt_diag.so   measurement-only kernels (stream ceilings, co-residency spinners, the round-1 register-sweep kernel): no header, no version.
+                          environment switches of DESIGN.md's appendix.  Same ABI.  Tests and A/B tools only (DKT_TWINS=1 + a variant switch).
+All but diag and twins are product code, built under the spill budget.  __graft_entry__.build() brings every library up to date: a failure raises, except for
+those `LibSpec.best_effort` marks (post .. twins), where it warns -- they are built on first load as well, and raise there.
 
-An object file's cache key hashes its source, every csrc/*.h, csrc/*.inc and csrc/*.def, include/dkt_abi.h and the ABI header of its own library -- what the sources
-include -- so an edit to one library's header recompiles that library only.
+An object file's cache key hashes its source, every *.h, *.inc and *.def of csrc/ (and of its own directory), include/dkt_abi.h and the ABI header of its own
+library -- what the sources include -- so an edit to one library's header recompiles that library only.
 
 Adding a library: one ABI header under include/, one signature dict, one `LibSpec` entry in `LIBS` (+ the one-line `load_*` / `build_*` names its callers want).
-
-Beside the table, `EXT_LIBS`: extension libraries, product code whose sources live under csrc_ext/ (`LibSpec.src_dir`; they include the headers of csrc/) and which go
-through the same operations:
-  loo    libdkt_loo.so    the leave-one-out predictive likelihood and its gradients (include/dkt_abi_loo.h; docs/LOO.md).
-And on its own (`POST_SPEC`, in neither dict), the same kind of library with the same operations:
-  post   libdkt_post.so   the joint posterior at test time: covariance, test likelihood, samples (include/dkt_abi_post.h; docs/POSTERIOR.md).
-  loofs  libdkt_loofs.so  (`LOOFS_SPEC`) the leave-one-out likelihood of the linear kernels in feature space: D <= 64, any number of rows (include/dkt_abi_loofs.h;
-                          docs/LOOFS.md).
 """
 from __future__ import annotations
 
@@ -149,14 +146,14 @@ DIAG_SIGNATURES = {
     "dkt_diag_mll_reg_f32": (_c_i, [_c_p, _c_p, ctypes.c_long, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_f, _c_i, ctypes.c_uint] + [_c_p] * 11),
 }
 
-# libdkt_loo.so (include/dkt_abi_loo.h; tests check that this lists every function of the header): an extension library, EXT_LIBS below
+# libdkt_loo.so (include/dkt_abi_loo.h; tests check that this lists every function of the header)
 LOO_SIGNATURES = {
     "dkt_loo_abi_version": (_c_i, []),
     "dkt_loo_f32": (_c_i, [_c_p, ctypes.c_long, ctypes.c_long, _c_p, ctypes.c_long] + [_c_p] * 4 + [_c_i, _c_i, _c_i, _c_f, _c_i, ctypes.c_uint] + [_c_p] * 11),
 }
 LOO_MAX_N, LOO_MAX_C = 127, 32      # the limits of include/dkt_abi_loo.h (DKT_ERR_SHAPE outside them)
 
-# libdkt_post.so (include/dkt_abi_post.h; tests check that this lists every function of the header): an extension library on its own, POST_SPEC below
+# libdkt_post.so (include/dkt_abi_post.h; tests check that this lists every function of the header)
 POST_SIGNATURES = {
     "dkt_post_abi_version": (_c_i, []),
     "dkt_posterior_workspace_bytes": (ctypes.c_size_t, [_c_i, _c_i, _c_i, _c_i]),
@@ -165,8 +162,7 @@ POST_SIGNATURES = {
 }
 POST_MAX_N, POST_MAX_M, POST_MAX_C = 127, 127, 32      # the limits of include/dkt_abi_post.h (DKT_ERR_SHAPE outside them)
 
-
-# libdkt_loofs.so (include/dkt_abi_loofs.h; tests check that this lists every function of the header): an extension library on its own, LOOFS_SPEC below
+# libdkt_loofs.so (include/dkt_abi_loofs.h; tests check that this lists every function of the header)
 LOOFS_SIGNATURES = {
     "dkt_loofs_abi_version": (_c_i, []),
     "dkt_loofs_workspace_bytes": (ctypes.c_size_t, [_c_i, _c_i, _c_i, _c_i]),
@@ -187,7 +183,8 @@ class LibSpec(NamedTuple):
     reload_symbol: Optional[str] = None     # makes the library re-read its environment switches (ops._sync_env)
     twins: bool = False                     # compiled with -DDKT_TWINS
     spill_budget: bool = True               # SPILL_BUDGET fails the build: product code (not the twins' non-default instantiations, not measurement kernels)
-    src_dir: Optional[str] = None           # where `sources` live when not under csrc/ (an extension library: EXT_LIBS)
+    src_dir: Optional[str] = None           # where `sources` live when not under csrc/ (an extension library)
+    best_effort: bool = False               # a failed build of it only warns in __graft_entry__.build() (it is built, and raises, on first load)
 
 
 def _so(stem: str) -> str:
@@ -196,9 +193,9 @@ def _so(stem: str) -> str:
 
 _ABI = dict(header="dkt_abi.h", version_macro="DKT_ABI_VERSION", version_symbol="dkt_abi_version", reload_symbol="dkt_reload_env",
             signatures=SIGNATURES, no_fallback="the DKT hot path has no CPU fallback.")
+CSRC_EXT = os.path.join(_HERE, "csrc_ext")
 LIBS = {
     "hip": LibSpec(_so("hip"), SOURCES, **_ABI),
-    "twins": LibSpec(_so("twins"), SOURCES, twins=True, spill_budget=False, **_ABI),
     "x16": LibSpec(_so("x16"), ["dkt_frontend_x16.hip"], X16_SIGNATURES, "16-bit trunk features have no fallback.", "dkt_abi_x16.h", "DKT_X16_ABI_VERSION",
                    "dkt_x16_abi_version", "dkt_x16_reload_env"),
     "data": LibSpec(_so("data"), ["dkt_augment.hip"], DATA_SIGNATURES, "image datasets have no CPU fallback.", "dkt_abi_data.h", "DKT_DATA_ABI_VERSION",
@@ -206,26 +203,20 @@ LIBS = {
     "smk": LibSpec(_so("smk"), ["dkt_smk_task.hip"], SMK_SIGNATURES, "there is no CPU fallback.", "dkt_abi_smk.h", "DKT_SMK_ABI_VERSION", "dkt_smk_abi_version"),
     "gpc": LibSpec(_so("gpc"), ["dkt_gpc.hip"], GPC_SIGNATURES, "Laplace GP classification on the device has no fallback.", "dkt_abi_gpc.h", "DKT_GPC_ABI_VERSION",
                    "dkt_gpc_abi_version"),
-    "diag": LibSpec(_so("diag"), ["dkt_diag.hip", "dkt_mll_reg_twin.hip"], DIAG_SIGNATURES, "the measurement kernels have no fallback.", spill_budget=False),
-}
-# Extension libraries: product code that stands beside the table of seven (sources under csrc_ext/, which may include the headers of csrc/), built by build_loo()
-# and on first load; the operations below take their specs like any other.
-CSRC_EXT = os.path.join(_HERE, "csrc_ext")
-EXT_LIBS = {
     "loo": LibSpec(_so("loo"), ["dkt_loo.hip"], LOO_SIGNATURES, "the leave-one-out objective has no fallback.", "dkt_abi_loo.h", "DKT_LOO_ABI_VERSION",
                    "dkt_loo_abi_version", src_dir=CSRC_EXT),
+    "post": LibSpec(_so("post"), ["dkt_posterior.hip"], POST_SIGNATURES, "the joint posterior has no fallback.", "dkt_abi_post.h", "DKT_POST_ABI_VERSION",
+                    "dkt_post_abi_version", src_dir=CSRC_EXT, best_effort=True),
+    "loofs": LibSpec(_so("loofs"), ["dkt_loo_lowrank.hip"], LOOFS_SIGNATURES, "the feature-space leave-one-out objective has no fallback.", "dkt_abi_loofs.h",
+                     "DKT_LOOFS_ABI_VERSION", "dkt_loofs_abi_version", src_dir=CSRC_EXT, best_effort=True),
+    "diag": LibSpec(_so("diag"), ["dkt_diag.hip", "dkt_mll_reg_twin.hip"], DIAG_SIGNATURES, "the measurement kernels have no fallback.", spill_budget=False,
+                    best_effort=True),
+    "twins": LibSpec(_so("twins"), SOURCES, twins=True, spill_budget=False, best_effort=True, **_ABI),
 }
-LOO_LIB_PATH = EXT_LIBS["loo"].path
-# The joint posterior at test time (docs/POSTERIOR.md): an extension library like the above, registered on its own -- in neither dict -- built by build_post() and
-# on first load.
-POST_SPEC = LibSpec(_so("post"), ["dkt_posterior.hip"], POST_SIGNATURES, "the joint posterior has no fallback.", "dkt_abi_post.h", "DKT_POST_ABI_VERSION",
-                    "dkt_post_abi_version", src_dir=CSRC_EXT)
-POST_LIB_PATH = POST_SPEC.path
-# The leave-one-out likelihood in feature space (docs/LOOFS.md): registered the same way, built by build_loofs() and on first load.
-LOOFS_SPEC = LibSpec(_so("loofs"), ["dkt_loo_lowrank.hip"], LOOFS_SIGNATURES, "the feature-space leave-one-out objective has no fallback.", "dkt_abi_loofs.h",
-                     "DKT_LOOFS_ABI_VERSION", "dkt_loofs_abi_version", src_dir=CSRC_EXT)
-LOOFS_LIB_PATH = LOOFS_SPEC.path
-LIB_PATH, TWINS_LIB_PATH, X16_LIB_PATH, DATA_LIB_PATH, SMK_LIB_PATH, GPC_LIB_PATH, DIAG_LIB_PATH = (LIBS[k].path for k in ("hip", "twins", "x16", "data", "smk", "gpc", "diag"))
+LIB_PATH, TWINS_LIB_PATH, X16_LIB_PATH, DATA_LIB_PATH, SMK_LIB_PATH, GPC_LIB_PATH, LOO_LIB_PATH, POST_LIB_PATH, LOOFS_LIB_PATH = (
+    LIBS[k].path for k in ("hip", "twins", "x16", "data", "smk", "gpc", "loo", "post", "loofs"))
+
+BUILT_WITH_PRODUCT = ("x16", "data", "smk", "gpc")          # what build() brings up to date beside "hip"; __graft_entry__.build() does the rest of the table
 
 _lock = threading.Lock()
 _libs = {}          # path -> bound CDLL; a library that is not in here yet has not had its staleness check in this process either
@@ -385,7 +376,7 @@ def _compile_link(spec: LibSpec, target: str = None, replace=None, verbose=False
             if f.endswith(".objects.json"):
                 with open(os.path.join(OBJ_DIR, f)) as fh:
                     keep.update(json.load(fh))
-        known = {src for lib in list(LIBS.values()) + list(EXT_LIBS.values()) + [POST_SPEC, LOOFS_SPEC] for src in lib.sources}
+        known = {src for lib in LIBS.values() for src in lib.sources}
         for f in os.listdir(OBJ_DIR):
             base = f[:-len(".res.json")] if f.endswith(".res.json") else f
             if base.endswith(".o") and base not in keep and any(base.startswith(src + ".") for src in known):
@@ -400,10 +391,15 @@ def _build_if_stale(spec: LibSpec, verbose: bool = False) -> str:
     return _compile_link(spec, verbose=verbose) if _stale(spec) else spec.path
 
 
+def build_lib(key: str, verbose: bool = False) -> str:
+    """Bring one library of the table up to date; its path."""
+    return _build_if_stale(LIBS[key], verbose)
+
+
 def build(force: bool = False, verbose: bool = False, out: str = None, replace: dict = None) -> str:
-    """hipcc --offload-arch=gfx950 -> deep-kernel-transfer_amd/libdkt_hip.so (in-tree), and the other product libraries (x16, data, smk, gpc) brought up to date as
-    well (their own stamps: they are built even when the product library is current).  Cross-compiles without a GPU.  `out` / `replace` ({source name: other
-    path}) build a variant library for A/B runs (the product library only)."""
+    """hipcc --offload-arch=gfx950 -> deep-kernel-transfer_amd/libdkt_hip.so (in-tree), and the other product libraries of csrc/ (x16, data, smk, gpc) brought up
+    to date as well (their own stamps: they are built even when the product library is current).  Cross-compiles without a GPU.  `out` / `replace` ({source
+    name: other path}) build a variant library for A/B runs (the product library only)."""
     path = LIB_PATH
     if out is not None or force or needs_build():
         if force and os.path.isdir(OBJ_DIR):
@@ -412,45 +408,29 @@ def build(force: bool = False, verbose: bool = False, out: str = None, replace: 
                     os.remove(os.path.join(OBJ_DIR, f))
         path = _compile_link(LIBS["hip"], out, replace, verbose)
     if out is None:
-        for key in ("x16", "data", "smk", "gpc"):
+        for key in BUILT_WITH_PRODUCT:
             _build_if_stale(LIBS[key], verbose)
     return path
 
 
-def build_x16(verbose: bool = False) -> str:
-    return _build_if_stale(LIBS["x16"], verbose)
-
-
-def build_data(verbose: bool = False) -> str:
-    return _build_if_stale(LIBS["data"], verbose)
-
-
-def build_smk(verbose: bool = False) -> str:
-    return _build_if_stale(LIBS["smk"], verbose)
-
-
 def build_gpc(verbose: bool = False) -> str:
-    return _build_if_stale(LIBS["gpc"], verbose)
+    return build_lib("gpc", verbose)
 
 
 def build_twins(verbose: bool = False) -> str:
-    return _build_if_stale(LIBS["twins"], verbose)
-
-
-def build_diag(verbose: bool = False) -> str:
-    return _build_if_stale(LIBS["diag"], verbose)
+    return build_lib("twins", verbose)
 
 
 def build_loo(verbose: bool = False) -> str:
-    return _build_if_stale(EXT_LIBS["loo"], verbose)
+    return build_lib("loo", verbose)
 
 
 def build_post(verbose: bool = False) -> str:
-    return _build_if_stale(POST_SPEC, verbose)
+    return build_lib("post", verbose)
 
 
 def build_loofs(verbose: bool = False) -> str:
-    return _build_if_stale(LOOFS_SPEC, verbose)
+    return build_lib("loofs", verbose)
 
 
 def _header_version(spec: LibSpec) -> int:
@@ -460,36 +440,40 @@ def _header_version(spec: LibSpec) -> int:
         return int(re.search(r"#define\s+%s\s+(\d+)" % spec.version_macro, fh.read()).group(1))
 
 
+def header_version(key: str) -> int:
+    return _header_version(LIBS[key])
+
+
 def abi_version_of_header() -> int:
-    return _header_version(LIBS["hip"])
+    return header_version("hip")
 
 
 def x16_abi_version_of_header() -> int:
-    return _header_version(LIBS["x16"])
+    return header_version("x16")
 
 
 def data_abi_version_of_header() -> int:
-    return _header_version(LIBS["data"])
+    return header_version("data")
 
 
 def smk_abi_version_of_header() -> int:
-    return _header_version(LIBS["smk"])
+    return header_version("smk")
 
 
 def gpc_abi_version_of_header() -> int:
-    return _header_version(LIBS["gpc"])
+    return header_version("gpc")
 
 
 def loo_abi_version_of_header() -> int:
-    return _header_version(EXT_LIBS["loo"])
+    return header_version("loo")
 
 
 def post_abi_version_of_header() -> int:
-    return _header_version(POST_SPEC)
+    return header_version("post")
 
 
 def loofs_abi_version_of_header() -> int:
-    return _header_version(LOOFS_SPEC)
+    return header_version("loofs")
 
 
 def device_code_objects(path: str = None) -> list:
@@ -625,9 +609,10 @@ def unprotected_wide_buffer_stores(path: str = None) -> list:
 
 
 def _load(spec: LibSpec, path: str = None) -> ctypes.CDLL:
-    """dlopen a library and bind every entry of its signature table; raises (never falls back) when it cannot be built or loaded, lacks a symbol, or implements
-    another ABI version than its header declares.  Without `path`, the library is first brought up to date where the sources are present: once per process (a
-    cached handle returns before that), and inside the lock, so that no thread dlopens a file that another one is replacing.  A `path` is loaded as it is."""
+    """dlopen a library and bind every entry of its signature table; raises (never falls back) when it cannot be built or loaded, lacks a symbol, or
+    implements another ABI version than its header declares.  Without `path`, the library is first brought up to date where the sources are present: once per
+    process (a cached handle returns before that), and inside the lock, so that no thread dlopens a file that another one is replacing.  A `path` is loaded as
+    it is."""
     with _lock:
         lib = _libs.get(path or spec.path)
         if lib is not None:
@@ -653,46 +638,50 @@ def _load(spec: LibSpec, path: str = None) -> ctypes.CDLL:
         return lib
 
 
+def load_lib(key: str, path: str = None) -> ctypes.CDLL:
+    return _load(LIBS[key], path)
+
+
 def load(path: str = None) -> ctypes.CDLL:
     """The product library -- or the build of its ABI that `path` / DKT_AMD_LIB names -- as it is: bringing it up to date is build()'s job (one rank's, in a
     multi-process run)."""
-    return _load(LIBS["hip"], path or _lib_path())
+    return load_lib("hip", path or _lib_path())
 
 
 def load_twins() -> ctypes.CDLL:
-    return _load(LIBS["twins"])
+    return load_lib("twins")
 
 
 def load_x16() -> ctypes.CDLL:
-    return _load(LIBS["x16"])
+    return load_lib("x16")
 
 
 def load_data() -> ctypes.CDLL:
-    return _load(LIBS["data"])
+    return load_lib("data")
 
 
 def load_smk() -> ctypes.CDLL:
-    return _load(LIBS["smk"])
+    return load_lib("smk")
 
 
 def load_gpc() -> ctypes.CDLL:
-    return _load(LIBS["gpc"])
+    return load_lib("gpc")
 
 
 def load_diag() -> ctypes.CDLL:
-    return _load(LIBS["diag"])
+    return load_lib("diag")
 
 
 def load_loo() -> ctypes.CDLL:
-    return _load(EXT_LIBS["loo"])
+    return load_lib("loo")
 
 
 def load_post() -> ctypes.CDLL:
-    return _load(POST_SPEC)
+    return load_lib("post")
 
 
 def load_loofs() -> ctypes.CDLL:
-    return _load(LOOFS_SPEC)
+    return load_lib("loofs")
 
 
 def reload_env(lib) -> None:

@@ -104,8 +104,8 @@ def test_signature_table_is_the_header():
 def test_gpc_is_a_product_library_of_the_table():
     spec = L.LIBS["gpc"]
     assert spec.sources == ["dkt_gpc.hip"] and spec.header == "dkt_abi_gpc.h" and spec.spill_budget and not spec.twins
-    assert len(L.LIBS) == 7 and L.abi_version_of_header() == 8                     # a seventh library; it adds nothing to the product ABI
-    assert "Seven in-tree shared objects" in L.__doc__
+    assert spec.src_dir is None and not spec.best_effort and "dkt_gpc.hip" not in L.SOURCES and L.abi_version_of_header() == 8      # it adds nothing to the product ABI
+    assert "libdkt_gpc.so" in L.__doc__
 
 
 def test_build_brings_gpc_up_to_date(monkeypatch):

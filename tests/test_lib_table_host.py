@@ -1,5 +1,6 @@
 """CPU-side checks of the loader table (dkt_amd._lib.LIBS): which sources and headers belong to which library, and what the one load path does for each."""
 import os
+import re
 
 import pytest
 
@@ -8,10 +9,43 @@ import dkt_amd
 L, ops = dkt_amd._lib, dkt_amd.ops
 
 
+KEYS = ["data", "diag", "gpc", "hip", "loo", "loofs", "post", "smk", "twins", "x16"]
+EXTENSIONS = ["loo", "loofs", "post"]
+
+
+def test_the_table_holds_every_library():
+    assert sorted(L.LIBS) == KEYS
+    assert sorted(k for k, spec in L.LIBS.items() if spec.src_dir) == EXTENSIONS and all(L.LIBS[k].src_dir == L.CSRC_EXT for k in EXTENSIONS)
+    assert len({spec.path for spec in L.LIBS.values()}) == len(KEYS)
+    # what a failed build of only warns about in __graft_entry__.build(); product code is built under the spill budget
+    assert sorted(k for k, spec in L.LIBS.items() if spec.best_effort) == ["diag", "loofs", "post", "twins"]
+    assert sorted(k for k, spec in L.LIBS.items() if not spec.spill_budget) == ["diag", "twins"]
+    # what build() brings up to date itself; __graft_entry__.build() loops over the rest
+    assert L.BUILT_WITH_PRODUCT == ("x16", "data", "smk", "gpc") and not [k for k in L.BUILT_WITH_PRODUCT if L.LIBS[k].best_effort or L.LIBS[k].src_dir]
+    assert [name for name in vars(L) if isinstance(getattr(L, name), L.LibSpec)] == []          # no spec stands beside the table
+
+
 def test_every_source_belongs_to_exactly_one_library():
-    owned = [s for key, spec in L.LIBS.items() if key != "twins" for s in spec.sources]
-    assert sorted(owned) == sorted(f for f in os.listdir(L.CSRC) if f.endswith(".hip"))
+    for src_dir in (L.CSRC, L.CSRC_EXT):
+        owned = [s for key, spec in L.LIBS.items() if key != "twins" and (spec.src_dir or L.CSRC) == src_dir for s in spec.sources]
+        assert sorted(owned) == sorted(f for f in os.listdir(src_dir) if f.endswith(".hip")), src_dir
     assert L.LIBS["twins"].sources is L.LIBS["hip"].sources
+
+
+def test_every_signature_table_is_its_header():
+    """For every library with a header: the functions the header declares are the keys of its signature table, with as many arguments."""
+    seen = 0
+    for key, spec in L.LIBS.items():
+        if spec.header is None:
+            continue
+        flat = re.sub(r"/\*.*?\*/", "", open(os.path.join(L.INCLUDE, spec.header)).read(), flags=re.S)
+        assert sorted(set(re.findall(r"\b(dkt_\w+)\s*\(", flat))) == sorted(spec.signatures), key
+        for name, (_, args) in spec.signatures.items():
+            proto = re.search(r"\b%s\s*\(([^)]*)\)" % name, flat).group(1).strip()
+            assert len(args) == (0 if proto == "void" else proto.count(",") + 1), (key, name)
+        assert spec.version_symbol in spec.signatures and L.header_version(key) >= 1, key
+        seen += 1
+    assert seen == len(KEYS) - 1 and L.LIBS["diag"].header is None
 
 
 def _stamp_with_edited(monkeypatch, key, header=None):
@@ -23,7 +57,8 @@ def _stamp_with_edited(monkeypatch, key, header=None):
 
 
 @pytest.mark.parametrize("key, header, changes", [("hip", "dkt_abi.h", True), ("hip", "dkt_abi_x16.h", False),
-                                                  ("smk", "dkt_abi_smk.h", True), ("smk", "dkt_abi.h", True), ("smk", "dkt_abi_data.h", False)])
+                                                  ("smk", "dkt_abi_smk.h", True), ("smk", "dkt_abi.h", True), ("smk", "dkt_abi_data.h", False),
+                                                  ("loofs", "dkt_abi_loofs.h", True), ("loofs", "dkt_abi_loo.h", False), ("hip", "dkt_abi_loofs.h", False)])
 def test_a_header_edit_restamps_the_libraries_that_include_it(monkeypatch, key, header, changes):
     assert os.path.exists(os.path.join(L.INCLUDE, header))
     assert (_stamp_with_edited(monkeypatch, key, header) != _stamp_with_edited(monkeypatch, key)) == changes

@@ -99,13 +99,11 @@ def test_signature_table_is_the_header():
     assert len(L.LOO_SIGNATURES["dkt_loo_f32"][1]) == 26
 
 
-def test_loo_stands_beside_the_table_of_seven():
-    assert "loo" not in L.LIBS and len(L.LIBS) == 7 and list(L.EXT_LIBS) == ["loo"]
-    spec = L.EXT_LIBS["loo"]
+def test_loo_is_an_extension_library_of_the_table():
+    spec = L.LIBS["loo"]
     assert spec.sources == ["dkt_loo.hip"] and spec.header == "dkt_abi_loo.h" and spec.spill_budget and not spec.twins
     assert spec.src_dir == L.CSRC_EXT and os.path.isfile(os.path.join(spec.src_dir, "dkt_loo.hip")) and spec.path == L.LOO_LIB_PATH
-    assert not os.path.exists(os.path.join(L.CSRC, "dkt_loo.hip"))
-    assert all(s.src_dir is None for s in L.LIBS.values())
+    assert not os.path.exists(os.path.join(L.CSRC, "dkt_loo.hip")) and "dkt_loo.hip" not in L.SOURCES and not spec.best_effort
     assert L.loo_abi_version_of_header() == 1 and L.abi_version_of_header() == 8
     assert not [line for line in open(os.path.join(L.CSRC, "dkt_switches.def")) if "LOO" in line]          # no environment switch of its own
 
@@ -114,12 +112,17 @@ def test_graft_build_brings_loo_up_to_date(monkeypatch):
     import __graft_entry__ as g
     built = []
     monkeypatch.setattr(L, "build", lambda force=False: built.append("build") or L.LIB_PATH)
-    monkeypatch.setattr(L, "build_loo", lambda verbose=False: built.append("build_loo") or L.LOO_LIB_PATH)
-    monkeypatch.setattr(L, "build_diag", lambda: None)
-    monkeypatch.setattr(L, "build_twins", lambda: None)
+
+    def build_lib(key):
+        built.append(key)
+        if key == "loo":
+            raise RuntimeError("hipcc failed on dkt_loo.hip")
+
+    monkeypatch.setattr(L, "build_lib", build_lib)
     monkeypatch.setattr(L, "load", lambda: type("Lib", (), {"dkt_abi_version": staticmethod(L.abi_version_of_header)}))
-    g.build()
-    assert built == ["build", "build_loo"]
+    with pytest.raises(RuntimeError, match="dkt_loo.hip"):      # product code: a failed build of it stops build()
+        g.build()
+    assert built[0] == "build" and built[-1] == "loo" and not [k for k in built[1:] if L.LIBS[k].best_effort]
 
 
 def test_library_exports_exactly_its_header_and_its_version(loo_path):

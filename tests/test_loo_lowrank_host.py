@@ -114,10 +114,9 @@ def test_signature_table_is_the_header():
     assert len(L.LOOFS_SIGNATURES["dkt_loofs_f32"][1]) == 27
 
 
-def test_loofs_stands_in_neither_table():
-    assert len(L.LIBS) == 7 and list(L.EXT_LIBS) == ["loo"]
-    spec = L.LOOFS_SPEC
-    assert spec not in L.LIBS.values() and spec not in L.EXT_LIBS.values()
+def test_loofs_is_an_extension_library_of_the_table():
+    spec = L.LIBS["loofs"]
+    assert "dkt_loo_lowrank.hip" not in L.SOURCES and not os.path.exists(os.path.join(L.CSRC, "dkt_loo_lowrank.hip"))
     assert spec.sources == ["dkt_loo_lowrank.hip"] and spec.header == "dkt_abi_loofs.h" and spec.spill_budget and not spec.twins
     assert spec.src_dir == L.CSRC_EXT and os.path.isfile(os.path.join(spec.src_dir, "dkt_loo_lowrank.hip")) and spec.path == L.LOOFS_LIB_PATH
     assert L.loofs_abi_version_of_header() == 1 and L.abi_version_of_header() == 8 and L.loo_abi_version_of_header() == 1
@@ -128,18 +127,17 @@ def test_graft_build_brings_loofs_up_to_date_inside_the_guard(monkeypatch, capsy
     import __graft_entry__ as g
     built = []
     monkeypatch.setattr(L, "build", lambda force=False: built.append("build") or L.LIB_PATH)
-    monkeypatch.setattr(L, "build_loo", lambda verbose=False: built.append("build_loo") or L.LOO_LIB_PATH)
 
-    def failing():
-        built.append("build_loofs")
-        raise RuntimeError("hipcc failed on dkt_loo_lowrank.hip")
+    def build_lib(key):
+        built.append(key)
+        if key == "loofs":
+            raise RuntimeError("hipcc failed on dkt_loo_lowrank.hip")
 
-    monkeypatch.setattr(L, "build_loofs", failing)
-    for name in ("build_post", "build_diag", "build_twins"):
-        monkeypatch.setattr(L, name, lambda name=name: built.append(name))
+    monkeypatch.setattr(L, "build_lib", build_lib)
     monkeypatch.setattr(L, "load", lambda: type("Lib", (), {"dkt_abi_version": staticmethod(L.abi_version_of_header)}))
     g.build()                                                    # a failed build of the extension warns and does not stop the product build
-    assert built == ["build", "build_loo", "build_post", "build_loofs", "build_diag", "build_twins"]
+    assert [k for k in built if k in ("build", "loo", "post", "loofs", "diag", "twins")] == ["build", "loo", "post", "loofs", "diag", "twins"]
+    assert sorted(built[1:]) == sorted(k for k in L.LIBS if k != "hip" and k not in L.BUILT_WITH_PRODUCT)          # the rest of the table: build() has done its own
     assert "libdkt_loofs.so not built" in capsys.readouterr().err
 
 

@@ -158,10 +158,9 @@ def test_signature_table_is_the_header():
     assert len(L.POST_SIGNATURES["dkt_posterior_f32"][1]) == 37
 
 
-def test_post_stands_beside_both_tables():
-    assert len(L.LIBS) == 7 and list(L.EXT_LIBS) == ["loo"]
-    assert all(s.path != L.POST_LIB_PATH and "dkt_posterior.hip" not in s.sources for s in list(L.LIBS.values()) + list(L.EXT_LIBS.values()))
-    spec = L.POST_SPEC
+def test_post_is_an_extension_library_of_the_table():
+    spec = L.LIBS["post"]
+    assert all(s.path != L.POST_LIB_PATH and "dkt_posterior.hip" not in s.sources for k, s in L.LIBS.items() if k != "post") and "dkt_posterior.hip" not in L.SOURCES
     assert spec.sources == ["dkt_posterior.hip"] and spec.header == "dkt_abi_post.h" and spec.spill_budget and not spec.twins
     assert spec.src_dir == L.CSRC_EXT and os.path.isfile(os.path.join(spec.src_dir, "dkt_posterior.hip")) and spec.path == L.POST_LIB_PATH
     assert os.path.basename(spec.path) == "libdkt_post.so" and not os.path.exists(os.path.join(L.CSRC, "dkt_posterior.hip"))
@@ -174,18 +173,16 @@ def test_graft_build_builds_it_after_loo_and_guarded(monkeypatch, capsys):
     import __graft_entry__ as g
     built = []
     monkeypatch.setattr(L, "build", lambda force=False: built.append("build") or L.LIB_PATH)
-    monkeypatch.setattr(L, "build_loo", lambda verbose=False: built.append("build_loo") or L.LOO_LIB_PATH)
 
-    def build_post():
-        built.append("build_post")
-        raise RuntimeError("no compiler today")
+    def build_lib(key):
+        built.append(key)
+        if key == "post":
+            raise RuntimeError("no compiler today")
 
-    monkeypatch.setattr(L, "build_post", build_post)
-    monkeypatch.setattr(L, "build_diag", lambda: built.append("build_diag"))
-    monkeypatch.setattr(L, "build_twins", lambda: built.append("build_twins"))
+    monkeypatch.setattr(L, "build_lib", build_lib)
     monkeypatch.setattr(L, "load", lambda: type("Lib", (), {"dkt_abi_version": staticmethod(L.abi_version_of_header)}))
     g.build()                                                                   # (a failed build of it warns and does not stop the product's)
-    assert built == ["build", "build_loo", "build_post", "build_diag", "build_twins"]
+    assert [k for k in built if k in ("build", "loo", "post", "diag", "twins")] == ["build", "loo", "post", "diag", "twins"]
     assert "libdkt_post.so not built: no compiler today" in capsys.readouterr().err
 
 
@@ -195,7 +192,7 @@ def test_library_exports_exactly_its_header_and_its_version(post_path):
     assert exports == _declared("dkt_abi_post.h")
     assert L.device_code_objects(post_path), "no gfx950 code object in the library"
     assert int(L.load_post().dkt_post_abi_version()) == L.post_abi_version_of_header() == 1
-    assert not os.path.exists(post_path + ".stamp") or not L._stale(L.POST_SPEC)
+    assert not os.path.exists(post_path + ".stamp") or not L._stale(L.LIBS["post"])
 
 
 def test_library_does_not_spill(post_path):
