@@ -1146,8 +1146,11 @@ def _lowrank_forward(z, y, sv_, mean_, noise_in, cw_, jitter0, max_tries, unit_r
     with _timed("dkt_lowrank_gram_f32"):
         st = lib.dkt_lowrank_gram_f32(_p(z), _p(y), y_bstride, _p(mean_), _p(a), _p(p), b_, c_, n, d, _stream())
     _lib.check(st, "dkt_lowrank_gram_f32")
-    # the D x D models.  Unit rows (cossim / bncossim): cond(K') <= 1 + sv lambda_max / noise with lambda_max far below the trace N the kappa guard of dkt_mll_f32 prices
-    # (N = 420 rows would trip it at sv > 1.2 for a true condition of a few hundred); rows without the promise keep the guard
+    # the D x D models.  Unit rows (cossim / bncossim): cond(K') <= 1 + sv lambda_max / noise, and the kappa guard of dkt_mll_f32 prices the trace N instead of
+    # lambda_max (N = 420 rows would trip it at sv > 1.2 for a true condition of a few hundred on batch-normalised rows).  Measured without the guard on aligned
+    # (non-negative) unit rows, where lambda_max is 0.35 .. 0.83 N: at cond(K_c) = 1.5e3 .. 1.04e4 (N = 420) and 4e2 .. 2.6e3 (N = 105) the worst errors against
+    # float64 are logp 2.7e-5 (limit 1e-4), alpha 3.3e-5 (5e-4), dZ 4.1e-5 (1e-3) -- tests/test_lowrank_gpu.py, the table of DESIGN.md 4.6; rows without the
+    # promise keep the guard
     out = mll(a, p, sv_, _zeros_cached(c_, dev), noise_, want_grad=True, cls_weight=cw_, jitter0=jitter0, max_tries=max_tries, no_kappa_guard=bool(unit_rows))
     logp = torch.empty((b_, c_), device=dev, dtype=torch.float32)
     alpha = torch.empty((b_, c_, n), device=dev, dtype=torch.float32)

@@ -16,6 +16,7 @@ import dirichlet_lowrank_model
 import dirichlet_model
 import episode_routes as er
 import guard_arena as ga
+import lowrank_model
 from test_image_data_gpu import MIXED
 from test_inference_gpu import PREDICT_PER_CLASS, PREDICT_SHARED, VARIANCE_CASES
 from test_laplace_grad_gpu import SHAPES as LAPLACE_SHAPES
@@ -491,6 +492,24 @@ for _i, _d in enumerate((4, 36, 60, 64)):
     for _j, _n in enumerate((80, 97, 130)):
         _b, _c = (1, 3, 5)[(_i + _j) % 3], (1, 5, 17, 20, 32)[(_i + 2 * _j) % 5]
         case("feature-space-B%d-C%d-N%d-D%d" % (_b, _c, _n, _d), _LOWRANK_CALLS, _feature_space(_b, _c, _n, _d), env=dict(DKT_LOWRANK="force"), zero=("out[0][3]", "out[0][4]"))
+
+
+def _lowrank_kernels(b, c, n, d):
+    """The gram, finish and backward calls themselves (no ops-level gate: N < 80 too) at the edge shapes of tests/lowrank_model.py: masked last row tile, padded
+    columns, every class-tile and class-step count."""
+    def make(dev):
+        inp = {k: torch.as_tensor(v).to(dev) for k, v in lowrank_model.inputs(c, n, d, b=b, y_per_episode=True).items()}
+
+        def call(p):
+            fwd = ops._lowrank_forward(p["z"], p["y"], p["sv"], p["mean"], p["noise"], p["cw"], 1e-6, 3, True)
+            return fwd, ops._lowrank_backward(p["z"], fwd["v"], fwd["t"], fwd["wd"], p["g"])
+        return inp, call
+    return make
+
+
+for _i, (_c, _n, _d) in enumerate(lowrank_model.GUARD_CASES):
+    _b = 2 + _i % 2
+    case("lowrank-kernels-B%d-C%d-N%d-D%d" % (_b, _c, _n, _d), _LOWRANK_CALLS, _lowrank_kernels(_b, _c, _n, _d))
 
 
 def _route(route):
