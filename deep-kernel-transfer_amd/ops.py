@@ -22,7 +22,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -90,6 +90,108 @@ def _p(t: Optional[torch.Tensor]):
 
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+# ------------------------------------------------------------------------------------------------
+# The front door of the per-class GP calls: ONE place that says what such a problem looks like (`_problem`), what element strides the C ABI gets for an operand
+# that is shared by the class models or has a class axis (`_class_strides`), and how outputs and workspaces are made (`_f32`, `_i32`, `_workspace`).  All of it
+# allocates through this module's `torch`: the guard arena (tests/guard_arena.py) swaps that attribute, an allocation made anywhere else escapes it.
+# ------------------------------------------------------------------------------------------------
+_OPTIONAL_HYPERS = ("cls_weight", "scale")     # may be None (the kernels take NULL: weight / scale 1); every other per-class vector is required
+
+
+class _Problem(NamedTuple):
+    """B episodes of C class models on N rows, validated and contiguous.  base: [B,N,N] (shared by the class models) or [B,C,N,N] (per_class), or None and
+    rows: [B,N,D]; y (and noise_rows, or None): [C,N] (every episode) or [B,C,N]; hypers: the per-class vectors, [C] each, in the order they were named."""
+    base: Optional[torch.Tensor]
+    rows: Optional[torch.Tensor]
+    y: torch.Tensor
+    noise_rows: Optional[torch.Tensor]
+    hypers: tuple
+    b: int
+    c: int
+    n: int
+    d: Optional[int]                  # columns of rows
+    per_class: bool
+    base_strides: Optional[tuple]     # (batch_stride, class_stride) of base, in elements
+    y_bstride: int                    # 0: y is shared by the episodes
+    nr_bstride: int
+    dev: torch.device
+
+
+def _class_strides(t: torch.Tensor, c: int, item_ndim: int = 2) -> tuple:
+    """(batch_stride, class_stride) in elements of a contiguous [B, ...item] (shared by the C class models: class stride 0) or [B, C, ...item]."""
+    size = 1
+    for s in t.shape[-item_ndim:]:
+        size *= s
+    return (c * size, size) if t.dim() == item_ndim + 2 else (size, 0)
+
+
+def _hypers(fn: str, c: int, hypers: dict) -> tuple:
+    """The per-class vectors of `fn`, each flattened to a contiguous [C]; None stays None where the ABI allows it."""
+    out = []
+    for name, h in hypers.items():
+        if h is None and name not in _OPTIONAL_HYPERS:
+            raise RuntimeError("%s: `%s` is required (only %s may be None)" % (fn, name, " / ".join(_OPTIONAL_HYPERS)))
+        if h is not None:
+            if isinstance(h, torch.Tensor) and h.dim() != 1:         # ([C,1], [1,C], a scalar: flattened; a [C] as it is, no view made on the launch-bound paths)
+                h = h.reshape(-1)
+            h = _req(h, name, 1)
+            if h.numel() != c:
+                raise RuntimeError("%s: `%s` must have C=%d elements, got %d" % (fn, name, c, h.numel()))
+        out.append(h)
+    return tuple(out)
+
+
+def _problem(fn: str, y, base=None, rows=None, noise_rows=None, base_name: str = "e", y_name: str = "y", **hypers) -> _Problem:
+    """Validate the operands of the per-class GP call `fn` (its public name, for the messages): a base matrix or rows, y, optionally noise_rows, and the
+    per-class vectors by name.  A vector may be None only under a name listed in _OPTIONAL_HYPERS (the ABI takes NULL for those): a call with another
+    optional vector adds its name there; any other None is refused by name.  Every rejection is a RuntimeError that starts with `fn` (or with dkt_amd.ops: where `_req` refuses a tensor)."""
+    d = strides = None
+    if rows is not None:
+        rows = _req(rows, "z", 3)
+        b, n, d = rows.shape
+        per_class, dev = False, rows.device
+    else:
+        base = _req(base, base_name)
+        if base.dim() not in (3, 4) or base.shape[-1] != base.shape[-2]:
+            raise RuntimeError("%s: %s must be [B,N,N] or [B,C,N,N], got %s" % (fn, base_name, tuple(base.shape)))
+        b, n = base.shape[0], base.shape[-1]
+        per_class, dev = base.dim() == 4, base.device
+    y = _req(y, y_name)
+    if y.dim() not in (2, 3) or y.shape[-1] != n or (y.dim() == 3 and y.shape[0] != b):
+        raise RuntimeError("%s: %s must be [C,N] or [B,C,N] with B=%d, N=%d, got %s" % (fn, y_name, b, n, tuple(y.shape)))
+    c = y.shape[-2]
+    if per_class and base.shape[1] != c:
+        raise RuntimeError("%s: a per-class %s must be [B,C=%d,N,N], got %s" % (fn, base_name, c, tuple(base.shape)))
+    if base is not None:
+        strides = _class_strides(base, c)
+    nr_bstride = 0
+    if noise_rows is not None:
+        noise_rows = _req(noise_rows, "noise_rows")
+        if noise_rows.dim() not in (2, 3) or tuple(noise_rows.shape[-2:]) != (c, n) or (noise_rows.dim() == 3 and noise_rows.shape[0] != b):
+            raise RuntimeError("%s: noise_rows must be [C,N] or [B,C,N] like %s %s, got %s" % (fn, y_name, tuple(y.shape), tuple(noise_rows.shape)))
+        nr_bstride = c * n if noise_rows.dim() == 3 else 0
+    return _Problem(base, rows, y, noise_rows, _hypers(fn, c, hypers), b, c, n, d, per_class, strides, c * n if y.dim() == 3 else 0, nr_bstride, dev)
+
+
+def _f32(dev, *shape) -> torch.Tensor:
+    return torch.empty(shape, device=dev, dtype=torch.float32)
+
+
+def _i32(dev, *shape) -> torch.Tensor:
+    return torch.empty(shape, device=dev, dtype=torch.int32)
+
+
+def _workspace(nbytes: int, dev=None) -> Optional[torch.Tensor]:
+    """The scratch of a library call from its *_workspace_bytes* query: None for 0, else float32 of (nbytes + 3) // 4 elements.  Every query -- csrc/:
+    dkt_mll_workspace_bytes_for (the plan of dkt_mll.hip over the band, tiled, blocked and generic counts), dkt_laplace_grad_, dkt_mll_rownoise_,
+    dkt_bn_param_grads_workspace_bytes; csrc_ext/: dkt_loofs_, dkt_posterior_workspace_bytes; libdkt_smk.so: dkt_smk_task_workspace_bytes -- returns a float
+    count times sizeof(float): 0 or a positive multiple of 4.  For those, the sizes this module used to spell out -- (nbytes + 3) // 4, (max(nbytes, 4) + 3) // 4,
+    nbytes // 4, max(nbytes, 4) // 4 -- are the same element count, a block of exactly nbytes (what the guard arena's placement verdict looks for).  They differ
+    at 0 only: smk_task_bwd took one float there.  Its query is 0 exactly for B, D or Q <= 0, which dkt_smk_task_bwd_f32 refuses (DKT_ERR_BAD_ARG) in the
+    same test that refuses a NULL workspace."""
+    return torch.empty((nbytes + 3) // 4, device=dev, dtype=torch.float32) if nbytes else None
 
 
 # Optional per-kernel timing (bench.py): HIP events recorded on the stream the kernel is launched on
@@ -217,46 +319,20 @@ def mll(e: torch.Tensor, y: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor, 
     """Exact-GP marginal log likelihood of C models per episode.  e:[B,N,N] (one base matrix shared by the class models) or
     [B,C,N,N] (one per class model: DKT_MLL_E_PER_CLASS -- then w is [B,C,N,N] too); y:[C,N] (shared) or [B,C,N].
     force_*: the parity-tested twins of the default kernels (DKT_MLL_FORCE_* of include/dkt_abi.h)."""
-    per_class = e.dim() == 4
-    e = _req(e, "e", 4 if per_class else 3)
-    b_, n, n2 = e.shape[0], e.shape[-2], e.shape[-1]
-    if n != n2:
-        raise RuntimeError("mll: e must be [B,N,N] or [B,C,N,N]")
-    y = _req(y, "y")
-    if y.dim() == 2:
-        c_, y_bstride = y.shape[0], 0
-    elif y.dim() == 3 and y.shape[0] == b_:
-        c_, y_bstride = y.shape[1], y.shape[1] * n
-    else:
-        raise RuntimeError("mll: y must be [C,N] or [B,C,N]")
-    if y.shape[-1] != n:
-        raise RuntimeError("mll: y last dim %d != N %d" % (y.shape[-1], n))
-    sv = _req(sv.reshape(-1), "sv", 1)
-    mean = _req(mean.reshape(-1), "mean", 1)
-    noise = _req(noise.reshape(-1), "noise", 1)
-    if not (sv.numel() == mean.numel() == noise.numel() == c_):
-        raise RuntimeError("mll: sv/mean/noise must have C=%d elements" % c_)
-    if per_class and e.shape[1] != c_:
-        raise RuntimeError("mll: per-class e must be [B,C=%d,N,N]" % c_)
-    dev = e.device
-    logp = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    alpha = torch.empty((b_, c_, n), device=dev, dtype=torch.float32)
-    jit = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    info = torch.empty((b_, c_), device=dev, dtype=torch.int32)
+    pr = _problem("mll", y, base=e, sv=sv, mean=mean, noise=noise, cls_weight=cls_weight)
+    e, y, (sv, mean, noise, cls_weight) = pr.base, pr.y, pr.hypers
+    b_, c_, n, per_class, y_bstride, dev = pr.b, pr.c, pr.n, pr.per_class, pr.y_bstride, pr.dev
+    logp, alpha, jit, info = _f32(dev, b_, c_), _f32(dev, b_, c_, n), _f32(dev, b_, c_), _i32(dev, b_, c_)
     flags = ((MLL_FORCE_GENERIC if force_generic else 0) | (MLL_FORCE_BLOCKED if force_blocked else 0) |
-             (MLL_FORCE_F32MFMA if force_f32mfma else 0) | (MLL_E_PER_CLASS if per_class else 0) | (MLL_FORCE_TILED if force_tiled else 0) | (MLL_FORCE_BAND if force_band else 0) | (MLL_NO_KAPPA_GUARD if no_kappa_guard else 0))
+             (MLL_FORCE_F32MFMA if force_f32mfma else 0) | MLL_E_PER_CLASS * per_class | (MLL_FORCE_TILED if force_tiled else 0) | (MLL_FORCE_BAND if force_band else 0) | (MLL_NO_KAPPA_GUARD if no_kappa_guard else 0))
     chol = w = dsv = dmean = dnoise = None
     if want_chol:
         flags |= MLL_WANT_CHOL
-        chol = torch.empty((b_, c_, n, n), device=dev, dtype=torch.float32)
+        chol = _f32(dev, b_, c_, n, n)
     if want_grad:
         flags |= MLL_WANT_GRAD
-        w = torch.empty((b_, c_, n, n) if per_class else (b_, n, n), device=dev, dtype=torch.float32)
-        dsv = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-        dmean = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-        dnoise = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    if cls_weight is not None:
-        cls_weight = _req(cls_weight.reshape(-1), "cls_weight", 1)
+        w = _f32(dev, *e.shape)                                # (in the layout of e: [B,N,N] summed over the classes, or [B,C,N,N])
+        dsv, dmean, dnoise = _f32(dev, b_, c_), _f32(dev, b_, c_), _f32(dev, b_, c_)
     if force_reg and n + 1 <= 128:                           # (beyond its range the call takes the default kernels, as DKT_MLL_FORCE_REG did)
         # the round-1 register-sweep kernel: a validation twin in the measurement library (libdkt_diag.so) since round 4, not part of the product ABI
         if per_class or force_generic or force_blocked or force_f32mfma:
@@ -269,7 +345,7 @@ def mll(e: torch.Tensor, y: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor, 
         return dict(logp=logp, alpha=alpha, jitter=jit, info=info, chol=chol, w=w, dsv=dsv, dmean=dmean, dnoise=dnoise)
     lib = _lib_now(want_twin=force_f32mfma)
     ws_bytes = int(lib.dkt_mll_workspace_bytes_for(b_, c_, n, flags))           # what THIS call needs (the flag-less query covers every flag combination)
-    ws = torch.empty((max(ws_bytes, 4) + 3) // 4, device=dev, dtype=torch.float32) if ws_bytes else None
+    ws = _workspace(ws_bytes, dev)
     with _timed("dkt_mll_f32"):
         st = lib.dkt_mll_f32(_p(e), _p(y), y_bstride, _p(sv), _p(mean), _p(noise), b_, c_, n,
                              float(jitter0), int(max_tries), flags, _p(cls_weight), _p(logp), _p(alpha),
@@ -367,20 +443,19 @@ def kernel_matrix(a: torch.Tensor, bm: Optional[torch.Tensor], kernel: str, leng
 def predict(ex: torch.Tensor, alpha: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor, want_labels: bool = True):
     """mu[b,c,q] = mean[c] + sv[c] sum_n ex[b,(c,)q,n] alpha[b,c,n]; labels[b,q] = argmax_c mu (first maximum wins).
     ex: [B,M,N] (one base cross kernel shared by the class models: dkt_predict_f32) or [B,C,M,N] (one per class model: dkt_predict_per_class_f32)."""
-    per_class = ex.dim() == 4
-    ex = _req(ex, "ex", 4 if per_class else 3)
+    ex = _req(ex, "ex")
     alpha = _req(alpha, "alpha", 3)
+    per_class, c_ = ex.dim() == 4, alpha.shape[1]
+    if ex.dim() not in (3, 4) or alpha.shape[0] != ex.shape[0] or alpha.shape[2] != ex.shape[-1] or (per_class and ex.shape[1] != c_):
+        raise RuntimeError("predict: ex must be [B,M,N] or [B,C,M,N] and alpha [B,C,N], got %s and %s" % (tuple(ex.shape), tuple(alpha.shape)))
     b_, m, n = ex.shape[0], ex.shape[-2], ex.shape[-1]
-    c_ = alpha.shape[1]
-    if alpha.shape[0] != b_ or alpha.shape[2] != n or (per_class and ex.shape[1] != c_):
-        raise RuntimeError("predict: alpha must be [B,C,N] (and a per-class ex [B,C,M,N])")
     sv = _req(sv.reshape(-1), "sv", 1)
     mean = _req(mean.reshape(-1), "mean", 1)
-    mu = torch.empty((b_, c_, m), device=ex.device, dtype=torch.float32)
-    labels = torch.empty((b_, m), device=ex.device, dtype=torch.int32) if want_labels else None
+    mu = _f32(ex.device, b_, c_, m)
+    labels = _i32(ex.device, b_, m) if want_labels else None
     lib = _lib_now()
-    fn, name = (lib.dkt_predict_per_class_f32, "dkt_predict_per_class_f32") if per_class else (lib.dkt_predict_f32, "dkt_predict_f32")
-    _lib.check(fn(_p(ex), _p(alpha), _p(sv), _p(mean), _p(mu), _p(labels), b_, c_, m, n, _stream()), name)
+    name = ("dkt_predict_f32", "dkt_predict_per_class_f32")[per_class]
+    _lib.check(getattr(lib, name)(_p(ex), _p(alpha), _p(sv), _p(mean), _p(mu), _p(labels), b_, c_, m, n, _stream()), name)
     return mu, labels
 
 
@@ -396,11 +471,8 @@ def predict_var(ex: torch.Tensor, exx: torch.Tensor, chol: torch.Tensor, sv: tor
         raise RuntimeError("predict_var: exx must be [B,M] = %s for ex %s, got %s" % ((b_, m), tuple(ex.shape), tuple(exx.shape)))
     if chol.shape[0] != b_ or chol.shape[2] != n or chol.shape[3] != n:
         raise RuntimeError("predict_var: chol must be [B,C,N,N] with B=%d, N=%d of ex %s, got %s" % (b_, n, tuple(ex.shape), tuple(chol.shape)))
-    sv = _req(sv.reshape(-1), "sv", 1)
-    noise = _req(noise.reshape(-1), "noise", 1)
-    if not (sv.numel() == noise.numel() == c_):
-        raise RuntimeError("predict_var: sv/noise must have C=%d elements, got %d / %d" % (c_, sv.numel(), noise.numel()))
-    var = torch.empty((b_, c_, m), device=ex.device, dtype=torch.float32)
+    sv, noise = _hypers("predict_var", c_, dict(sv=sv, noise=noise))
+    var = _f32(ex.device, b_, c_, m)
     lib = _lib_now()
     _lib.check(lib.dkt_predict_var_f32(_p(ex), _p(exx), _p(chol), _p(sv), _p(noise), _p(var), b_, c_, m, n, _stream()),
                "dkt_predict_var_f32")
@@ -577,7 +649,7 @@ def smk_task_bwd(ge: torch.Tensor, x: torch.Tensor, weights: torch.Tensor, means
     dw = torch.empty((q,), device=x.device, dtype=torch.float32)
     dm = torch.empty((q, d), device=x.device, dtype=torch.float32)
     ds = torch.empty((q, d), device=x.device, dtype=torch.float32)
-    ws = torch.empty((max(int(lib.dkt_smk_task_workspace_bytes(b_, n, d, q)), 4) // 4,), device=x.device, dtype=torch.float32)
+    ws = _workspace(int(lib.dkt_smk_task_workspace_bytes(b_, n, d, q)), x.device)
     with _timed("dkt_smk_task_bwd_f32"):
         st = lib.dkt_smk_task_bwd_f32(_p(ge), _p(x), _p(weights), _p(means), _p(scales), _p(dx), _p(dw), _p(dm), _p(ds), _p(ws), b_, n, d, q,
                                       _stream())
@@ -635,19 +707,12 @@ def laplace_mode(K: torch.Tensor, Y: torch.Tensor, max_iter: int = 100) -> dict:
     K: [B,N,N] (shared by the C problems of an episode) or [B,C,N,N]; Y: targets in {0,1}, [C,N] (every episode) or [B,C,N].
     Returns dict(f [B,C,N], g = y - pi [B,C,N], w_sr = W^1/2 [B,C,N], chol = L [B,C,N,N], lml [B,C], iters [B,C] int32): g, w_sr, chol are those of
     the last executed iteration and S = W^1/2 B^-1 W^1/2 = (L^-1 diag(w_sr))^T (L^-1 diag(w_sr)); `laplace_predict` solves with L instead of forming S."""
-    per_class = K.dim() == 4
-    K = _req(K, "K", 4 if per_class else 3)
-    Y = _req(Y, "Y", Y.dim() if Y.dim() in (2, 3) else 2)
-    b_, n = K.shape[0], K.shape[-1]
-    c_ = Y.shape[-2]
-    if K.shape[-2] != n or Y.shape[-1] != n or (per_class and K.shape[1] != c_) or (Y.dim() == 3 and Y.shape[0] != b_):
-        raise RuntimeError("laplace_mode: K must be [B,N,N] or [B,C,N,N] and Y [C,N] or [B,C,N], got %s and %s" % (tuple(K.shape), tuple(Y.shape)))
-    dev = K.device
-    out = dict(f=torch.empty((b_, c_, n), device=dev, dtype=torch.float32), g=torch.empty((b_, c_, n), device=dev, dtype=torch.float32),
-               w_sr=torch.empty((b_, c_, n), device=dev, dtype=torch.float32), chol=torch.empty((b_, c_, n, n), device=dev, dtype=torch.float32),
-               lml=torch.empty((b_, c_), device=dev, dtype=torch.float32), iters=torch.empty((b_, c_), device=dev, dtype=torch.int32))
+    pr = _problem("laplace_mode", Y, base=K, base_name="K", y_name="Y")
+    b_, c_, n, dev = pr.b, pr.c, pr.n, pr.dev
+    out = dict(f=_f32(dev, b_, c_, n), g=_f32(dev, b_, c_, n), w_sr=_f32(dev, b_, c_, n), chol=_f32(dev, b_, c_, n, n), lml=_f32(dev, b_, c_),
+               iters=_i32(dev, b_, c_))
     with _timed("dkt_gpc_mode_f32"):
-        st = _lib.load_gpc().dkt_gpc_mode_f32(_p(K), (c_ if per_class else 1) * n * n, n * n if per_class else 0, _p(Y), c_ * n if Y.dim() == 3 else 0,
+        st = _lib.load_gpc().dkt_gpc_mode_f32(_p(pr.base), *pr.base_strides, _p(pr.y), pr.y_bstride,
                                               _p(out["f"]), _p(out["g"]), _p(out["w_sr"]), _p(out["chol"]), _p(out["lml"]), _p(out["iters"]),
                                               b_, c_, n, int(max_iter), _stream())
     _lib.check(st, "dkt_gpc_mode_f32")
@@ -658,22 +723,18 @@ def laplace_predict(Ks: torch.Tensor, kss: torch.Tensor, mode: dict):
     """Latent mean and variance, class probability and one-vs-rest label at M query points, ONE launch (scikit-learn's binary `predict_proba` per
     class and `OneVsRestClassifier.predict`).  Ks: cross kernel [B,M,N] or [B,C,M,N]; kss: prior variance of the queries [B,M] or [B,C,M]; mode: of
     `laplace_mode`.  Returns (mu, var, prob [B,C,M], labels [B,M] int32: the LAST of several equal maxima of prob; C == 1: mu > 0)."""
-    ks_pc, kss_pc = Ks.dim() == 4, kss.dim() == 3
-    Ks = _req(Ks, "Ks", 4 if ks_pc else 3)
-    kss = _req(kss, "kss", 3 if kss_pc else 2)
+    Ks, kss = _req(Ks, "Ks"), _req(kss, "kss")
     g, w_sr, chol = _req(mode["g"], "mode['g']", 3), _req(mode["w_sr"], "mode['w_sr']", 3), _req(mode["chol"], "mode['chol']", 4)
     b_, c_, n = g.shape
-    m = Ks.shape[-2]
-    if (Ks.shape[0] != b_ or Ks.shape[-1] != n or (ks_pc and Ks.shape[1] != c_) or kss.shape[0] != b_ or kss.shape[-1] != m or (kss_pc and kss.shape[1] != c_)
+    m = Ks.shape[-2] if Ks.dim() in (3, 4) else -1
+    if (tuple(Ks.shape) not in ((b_, m, n), (b_, c_, m, n)) or tuple(kss.shape) not in ((b_, m), (b_, c_, m))
             or tuple(w_sr.shape) != (b_, c_, n) or tuple(chol.shape) != (b_, c_, n, n)):
         raise RuntimeError("laplace_predict: Ks %s / kss %s do not fit a mode of B=%d, C=%d, N=%d" % (tuple(Ks.shape), tuple(kss.shape), b_, c_, n))
     dev = Ks.device
-    mu, var, prob = (torch.empty((b_, c_, m), device=dev, dtype=torch.float32) for _ in range(3))
-    labels = torch.empty((b_, m), device=dev, dtype=torch.int32)
+    mu, var, prob, labels = _f32(dev, b_, c_, m), _f32(dev, b_, c_, m), _f32(dev, b_, c_, m), _i32(dev, b_, m)
     with _timed("dkt_gpc_predict_f32"):
-        st = _lib.load_gpc().dkt_gpc_predict_f32(_p(Ks), (c_ if ks_pc else 1) * m * n, m * n if ks_pc else 0, _p(kss), (c_ if kss_pc else 1) * m,
-                                                 m if kss_pc else 0, _p(g), _p(w_sr), _p(chol), _p(mu), _p(var), _p(prob), _p(labels), b_, c_, m, n,
-                                                 _stream())
+        st = _lib.load_gpc().dkt_gpc_predict_f32(_p(Ks), *_class_strides(Ks, c_), _p(kss), *_class_strides(kss, c_, 1), _p(g), _p(w_sr), _p(chol),
+                                                 _p(mu), _p(var), _p(prob), _p(labels), b_, c_, m, n, _stream())
     _lib.check(st, "dkt_gpc_predict_f32")
     return mu, var, prob, labels
 
@@ -683,27 +744,17 @@ def laplace_grad(K: torch.Tensor, Y: torch.Tensor, f_hat: torch.Tensor, cls_weig
     C problems of an episode) or [B,C,N,N]; the covariance of problem (b, c) is scale[c] * K; Y in {0,1}: [C,N] or [B,C,N]; f_hat [B,C,N] of
     `laplace_mode` on those covariances.  Returns (lml [B,C] unweighted, dK = cls_weight_c scale_c d lml / d K_c -- [B,C,N,N], or [B,N,N] summed over the
     classes for a shared K --, dscale [B,C] = cls_weight_c <d lml / d K_c, K>)."""
-    per_class = K.dim() == 4
-    K = _req(K, "K", 4 if per_class else 3)
-    Y = _req(Y, "Y", Y.dim() if Y.dim() in (2, 3) else 2)
+    pr = _problem("laplace_grad", Y, base=K, base_name="K", y_name="Y", cls_weight=cls_weight, scale=scale)
+    (cw, sc), b_, c_, n, dev = pr.hypers, pr.b, pr.c, pr.n, pr.dev
     f_hat = _req(f_hat, "f_hat", 3)
-    b_, c_, n = f_hat.shape
-    if (K.shape[0] != b_ or K.shape[-1] != n or K.shape[-2] != n or (per_class and K.shape[1] != c_) or tuple(Y.shape[-2:]) != (c_, n)
-            or (Y.dim() == 3 and Y.shape[0] != b_)):
-        raise RuntimeError("laplace_grad: K %s / Y %s do not fit f_hat %s" % (tuple(K.shape), tuple(Y.shape), tuple(f_hat.shape)))
-    cw = None if cls_weight is None else _req(cls_weight.reshape(-1), "cls_weight", 1)
-    sc = None if scale is None else _req(scale.reshape(-1), "scale", 1)
-    if (cw is not None and cw.numel() != c_) or (sc is not None and sc.numel() != c_):
-        raise RuntimeError("laplace_grad: cls_weight / scale must have C=%d elements" % c_)
-    dev = K.device
-    lml = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    dscale = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    dk = torch.empty((b_, c_, n, n) if per_class else (b_, n, n), device=dev, dtype=torch.float32)
+    if tuple(f_hat.shape) != (b_, c_, n):
+        raise RuntimeError("laplace_grad: f_hat must be [B,C,N] = %s of K and Y, got %s" % ((b_, c_, n), tuple(f_hat.shape)))
+    lml, dscale, dk = _f32(dev, b_, c_), _f32(dev, b_, c_), _f32(dev, *pr.base.shape)
     lib = _lib_now()
-    ws_bytes = 0 if per_class else int(lib.dkt_laplace_grad_workspace_bytes(b_, c_, n))
-    ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32) if ws_bytes else None
+    ws_bytes = 0 if pr.per_class else int(lib.dkt_laplace_grad_workspace_bytes(b_, c_, n))
+    ws = _workspace(ws_bytes, dev)
     with _timed("dkt_laplace_grad_f32"):
-        st = lib.dkt_laplace_grad_f32(_p(K), (c_ if per_class else 1) * n * n, n * n if per_class else 0, _p(sc), _p(Y), c_ * n if Y.dim() == 3 else 0,
+        st = lib.dkt_laplace_grad_f32(_p(pr.base), *pr.base_strides, _p(sc), _p(pr.y), pr.y_bstride,
                                       _p(f_hat), _p(cw), _p(lml), _p(dk), _p(dscale), b_, c_, n, _p(ws), ws_bytes, _stream())
     _lib.check(st, "dkt_laplace_grad_f32")
     return lml, dk, dscale
@@ -736,41 +787,22 @@ def mll_rownoise(e: torch.Tensor, y: torch.Tensor, noise_rows: torch.Tensor, sv:
     e: [B,N,N] (shared by the class models) or [B,C,N,N]; y, noise_rows: [C,N] (every episode) or [B,C,N]; sv, mean: C elements.
     Returns dict(logp [B,C] unweighted, alpha [B,C,N], info [B,C] int32, chol [B,C,N,N] | None, and with want_grad de = cls_weight_c sv_c G_c ([B,C,N,N], or
     [B,N,N] summed over the classes for a shared e), dsv = cls_weight_c <G_c, e>, dmean = cls_weight_c sum alpha [B,C]), G = d logp / d K."""
-    per_class = e.dim() == 4
-    e = _req(e, "e", 4 if per_class else 3)
-    b_, n = e.shape[0], e.shape[-1]
-    y = _req(y, "y", y.dim() if y.dim() in (2, 3) else 2)
-    noise_rows = _req(noise_rows, "noise_rows", noise_rows.dim() if noise_rows.dim() in (2, 3) else 2)
-    c_ = y.shape[-2]
-    if (e.shape[-2] != n or y.shape[-1] != n or tuple(noise_rows.shape[-2:]) != (c_, n) or (per_class and e.shape[1] != c_)
-            or (y.dim() == 3 and y.shape[0] != b_) or (noise_rows.dim() == 3 and noise_rows.shape[0] != b_)):
-        raise RuntimeError("mll_rownoise: e must be [B,N,N] or [B,C,N,N] and y, noise_rows [C,N] or [B,C,N], got %s, %s and %s"
-                           % (tuple(e.shape), tuple(y.shape), tuple(noise_rows.shape)))
-    sv = _req(sv.reshape(-1), "sv", 1)
-    mean = _req(mean.reshape(-1), "mean", 1)
-    cw = None if cls_weight is None else _req(cls_weight.reshape(-1), "cls_weight", 1)
-    if not (sv.numel() == mean.numel() == c_) or (cw is not None and cw.numel() != c_):
-        raise RuntimeError("mll_rownoise: sv / mean / cls_weight must have C=%d elements" % c_)
-    dev = e.device
-    logp = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    alpha = torch.empty((b_, c_, n), device=dev, dtype=torch.float32)
-    info = torch.empty((b_, c_), device=dev, dtype=torch.int32)
+    pr = _problem("mll_rownoise", y, base=e, noise_rows=noise_rows, sv=sv, mean=mean, cls_weight=cls_weight)
+    (sv, mean, cw), b_, c_, n, dev = pr.hypers, pr.b, pr.c, pr.n, pr.dev
+    logp, alpha, info = _f32(dev, b_, c_), _f32(dev, b_, c_, n), _i32(dev, b_, c_)
     flags = (MLL_WANT_GRAD if want_grad else 0) | (MLL_WANT_CHOL if want_chol else 0)
-    chol = torch.empty((b_, c_, n, n), device=dev, dtype=torch.float32) if want_chol else None
-    de = dsv = dmean = ws = None
+    chol = _f32(dev, b_, c_, n, n) if want_chol else None
+    de = dsv = dmean = None
     ws_bytes = 0
     lib = _lib_now()
     if want_grad:
-        de = torch.empty((b_, c_, n, n) if per_class else (b_, n, n), device=dev, dtype=torch.float32)
-        dsv = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-        dmean = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-        if not per_class:
+        de, dsv, dmean = _f32(dev, *pr.base.shape), _f32(dev, b_, c_), _f32(dev, b_, c_)
+        if not pr.per_class:
             ws_bytes = int(lib.dkt_mll_rownoise_workspace_bytes(b_, c_, n))
-            ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32) if ws_bytes else None
+    ws = _workspace(ws_bytes, dev)
     with _timed("dkt_mll_rownoise_f32"):
-        st = lib.dkt_mll_rownoise_f32(_p(e), (c_ if per_class else 1) * n * n, n * n if per_class else 0, _p(y), c_ * n if y.dim() == 3 else 0,
-                                      _p(noise_rows), c_ * n if noise_rows.dim() == 3 else 0, _p(sv), _p(mean), _p(cw), _p(logp), _p(alpha), _p(de),
-                                      _p(dsv), _p(dmean), _p(chol), _p(info), b_, c_, n, flags, _p(ws), ws_bytes, _stream())
+        st = lib.dkt_mll_rownoise_f32(_p(pr.base), *pr.base_strides, _p(pr.y), pr.y_bstride, _p(pr.noise_rows), pr.nr_bstride, _p(sv), _p(mean), _p(cw),
+                                      _p(logp), _p(alpha), _p(de), _p(dsv), _p(dmean), _p(chol), _p(info), b_, c_, n, flags, _p(ws), ws_bytes, _stream())
     _lib.check(st, "dkt_mll_rownoise_f32")
     return dict(logp=logp, alpha=alpha, info=info, chol=chol, de=de, dsv=dsv, dmean=dmean)
 
@@ -784,6 +816,12 @@ def loo_supported(n: int, c: int) -> bool:
     return 1 <= n <= _lib.LOO_MAX_N and 1 <= c <= _lib.LOO_MAX_C
 
 
+def _loo_outputs(pr: _Problem):
+    """loo [B,C], alpha, mu_loo, var_loo [B,C,N], jitter [B,C], info [B,C] int32 of `loo` / `loo_lowrank`."""
+    b_, c_, n, dev = pr.b, pr.c, pr.n, pr.dev
+    return _f32(dev, b_, c_), _f32(dev, b_, c_, n), _f32(dev, b_, c_, n), _f32(dev, b_, c_, n), _f32(dev, b_, c_), _i32(dev, b_, c_)
+
+
 def loo(e: torch.Tensor, y: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor, noise: torch.Tensor, want_grad: bool = False,
         cls_weight: Optional[torch.Tensor] = None, jitter0: float = 1e-6, max_tries: int = 3) -> dict:
     """Leave-one-out predictive log likelihood of C exact-GP models per episode, K_c = sv_c E + noise_c I (dkt_loo_f32: ONE launch, the jitter ladder of
@@ -791,31 +829,15 @@ def loo(e: torch.Tensor, y: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor, 
     C elements.  Returns dict(loo [B,C] unweighted, alpha, mu_loo, var_loo [B,C,N] -- the leave-one-out predictive mean and variance of every row --,
     jitter [B,C], info [B,C] int32 (0 = ok; otherwise every output of that problem is NaN), and with want_grad w = cls_weight_c sv_c d loo / d K_c
     ([B,C,N,N], or [B,N,N] summed over the classes for a shared e), dsv, dmean, dnoise [B,C] raw, as `mll` reports its own)."""
-    per_class = e.dim() == 4
-    e = _req(e, "e", 4 if per_class else 3)
-    b_, n = e.shape[0], e.shape[-1]
-    y = _req(y, "y", y.dim() if y.dim() in (2, 3) else 2)
-    c_ = y.shape[-2]
-    if e.shape[-2] != n or y.shape[-1] != n or (per_class and e.shape[1] != c_) or (y.dim() == 3 and y.shape[0] != b_):
-        raise RuntimeError("loo: e must be [B,N,N] or [B,C,N,N] and y [C,N] or [B,C,N], got %s and %s" % (tuple(e.shape), tuple(y.shape)))
-    sv = _req(sv.reshape(-1), "sv", 1)
-    mean = _req(mean.reshape(-1), "mean", 1)
-    noise = _req(noise.reshape(-1), "noise", 1)
-    cw = None if cls_weight is None else _req(cls_weight.reshape(-1), "cls_weight", 1)
-    if not (sv.numel() == mean.numel() == noise.numel() == c_) or (cw is not None and cw.numel() != c_):
-        raise RuntimeError("loo: sv / mean / noise / cls_weight must have C=%d elements" % c_)
-    dev = e.device
-    val = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    alpha, mu, var = (torch.empty((b_, c_, n), device=dev, dtype=torch.float32) for _ in range(3))
-    jit = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    info = torch.empty((b_, c_), device=dev, dtype=torch.int32)
+    pr = _problem("loo", y, base=e, sv=sv, mean=mean, noise=noise, cls_weight=cls_weight)
+    (sv, mean, noise, cw), b_, c_, dev = pr.hypers, pr.b, pr.c, pr.dev
+    val, alpha, mu, var, jit, info = _loo_outputs(pr)
     w = dsv = dmean = dnoise = None
     if want_grad:
-        w = torch.empty((b_, c_, n, n) if per_class else (b_, n, n), device=dev, dtype=torch.float32)
-        dsv, dmean, dnoise = (torch.empty((b_, c_), device=dev, dtype=torch.float32) for _ in range(3))
+        w, dsv, dmean, dnoise = _f32(dev, *pr.base.shape), _f32(dev, b_, c_), _f32(dev, b_, c_), _f32(dev, b_, c_)
     with _timed("dkt_loo_f32"):
-        st = _lib.load_loo().dkt_loo_f32(_p(e), (c_ if per_class else 1) * n * n, n * n if per_class else 0, _p(y), c_ * n if y.dim() == 3 else 0, _p(sv), _p(mean),
-                                         _p(noise), _p(cw), b_, c_, n, float(jitter0), int(max_tries), LOO_WANT_GRAD if want_grad else 0, _p(val), _p(alpha),
+        st = _lib.load_loo().dkt_loo_f32(_p(pr.base), *pr.base_strides, _p(pr.y), pr.y_bstride, _p(sv), _p(mean), _p(noise), _p(cw),
+                                         b_, c_, pr.n, float(jitter0), int(max_tries), LOO_WANT_GRAD if want_grad else 0, _p(val), _p(alpha),
                                          _p(mu), _p(var), _p(w), _p(dsv), _p(dmean), _p(dnoise), _p(jit), _p(info), _stream())
     _lib.check(st, "dkt_loo_f32")
     return dict(loo=val, alpha=alpha, mu_loo=mu, var_loo=var, w=w, dsv=dsv, dmean=dmean, dnoise=dnoise, jitter=jit, info=info)
@@ -842,32 +864,18 @@ def loo_lowrank(z: torch.Tensor, y: torch.Tensor, sv: torch.Tensor, mean: torch.
     """`loo` for the linear kernels on the rows themselves, K_c = sv_c Z Z^T + noise_c I (dkt_loofs_f32: ONE launch, the jitter ladder inside the kernel on the
     D x D matrix Z^T Z + (noise_c + jitter) / sv_c I; D <= 64, any N: no N x N matrix exists).  z: [B,N,D]; y: [C,N] (every episode) or [B,C,N]; sv, mean, noise:
     C elements.  Returns the dict of `loo` with dz [B,N,D] = sum_c cls_weight_c d loo_c / d Z in the place of w (None without want_grad, like dsv, dmean, dnoise)."""
-    z = _req(z, "z", 3)
-    b_, n, d = z.shape
-    y = _req(y, "y", y.dim() if y.dim() in (2, 3) else 2)
-    c_ = y.shape[-2]
-    if y.shape[-1] != n or (y.dim() == 3 and y.shape[0] != b_):
-        raise RuntimeError("loo_lowrank: z must be [B,N,D] and y [C,N] or [B,C,N], got %s and %s" % (tuple(z.shape), tuple(y.shape)))
-    sv = _req(sv.reshape(-1), "sv", 1)
-    mean = _req(mean.reshape(-1), "mean", 1)
-    noise = _req(noise.reshape(-1), "noise", 1)
-    cw = None if cls_weight is None else _req(cls_weight.reshape(-1), "cls_weight", 1)
-    if not (sv.numel() == mean.numel() == noise.numel() == c_) or (cw is not None and cw.numel() != c_):
-        raise RuntimeError("loo_lowrank: sv / mean / noise / cls_weight must have C=%d elements" % c_)
-    dev = z.device
-    val = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    alpha, mu, var = (torch.empty((b_, c_, n), device=dev, dtype=torch.float32) for _ in range(3))
-    jit = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    info = torch.empty((b_, c_), device=dev, dtype=torch.int32)
+    pr = _problem("loo_lowrank", y, rows=z, sv=sv, mean=mean, noise=noise, cls_weight=cls_weight)
+    z, (sv, mean, noise, cw), b_, c_, n, d, dev = pr.rows, pr.hypers, pr.b, pr.c, pr.n, pr.d, pr.dev
+    val, alpha, mu, var, jit, info = _loo_outputs(pr)
     dz = dsv = dmean = dnoise = None
     if want_grad:
         dz = torch.empty_like(z)
-        dsv, dmean, dnoise = (torch.empty((b_, c_), device=dev, dtype=torch.float32) for _ in range(3))
+        dsv, dmean, dnoise = _f32(dev, b_, c_), _f32(dev, b_, c_), _f32(dev, b_, c_)
     lib = _lib.load_loofs()
     ws_bytes = int(lib.dkt_loofs_workspace_bytes(b_, c_, n, d))
-    ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.float32) if ws_bytes else None
+    ws = _workspace(ws_bytes, dev)
     with _timed("dkt_loofs_f32"):
-        st = lib.dkt_loofs_f32(_p(z), _p(y), c_ * n if y.dim() == 3 else 0, _p(sv), _p(mean), _p(noise), _p(cw), b_, c_, n, d, float(jitter0), int(max_tries),
+        st = lib.dkt_loofs_f32(_p(z), _p(pr.y), pr.y_bstride, _p(sv), _p(mean), _p(noise), _p(cw), b_, c_, n, d, float(jitter0), int(max_tries),
                                LOO_WANT_GRAD if want_grad else 0, _p(val), _p(alpha), _p(mu), _p(var), _p(dz), _p(dsv), _p(dmean), _p(dnoise), _p(jit), _p(info),
                                _p(ws), ws_bytes, _stream())
     _lib.check(st, "dkt_loofs_f32")
@@ -905,28 +913,23 @@ def posterior(e_ss: torch.Tensor, e_qs: torch.Tensor, e_qq: torch.Tensor, y: tor
     if not posterior_supported(n, m, c_):
         raise RuntimeError("posterior: N = %d support rows, M = %d query rows, C = %d models: dkt_posterior_f32 serves 1 <= N <= %d, 1 <= M <= %d, 1 <= C <= %d"
                            % (n, m, c_, _lib.POST_MAX_N, _lib.POST_MAX_M, _lib.POST_MAX_C))
-    e_ss, e_qs, e_qq = _req(e_ss, "e_ss"), _req(e_qs, "e_qs"), _req(e_qq, "e_qq")
-    y = _req(y, "y")
-    sv, mean, noise = _req(sv.reshape(-1), "sv", 1), _req(mean.reshape(-1), "mean", 1), _req(noise.reshape(-1), "noise", 1)
+    pr = _problem("posterior", y, base=e_ss, base_name="e_ss", sv=sv, mean=mean, noise=noise)       # (the shapes are settled above, before any tensor is refused)
+    e_qs, e_qq, (sv, mean, noise), dev = _req(e_qs, "e_qs"), _req(e_qq, "e_qq"), pr.hypers, pr.dev
     yq = None if yq is None else _req(yq, "yq", 3)
     s_ = 0 if eps is None else eps.shape[2]
     eps = None if s_ == 0 else _req(eps, "eps", 4)
-    dev = e_ss.device
-    f32 = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)      # noqa: E731
-    mu = f32(b_, c_, m)
-    cov = f32(b_, c_, m, m) if want_cov else None
-    chol = f32(b_, c_, m, m) if want_chol else None
-    logp, lpd = (f32(b_, c_), f32(b_, c_)) if yq is not None else (None, None)
-    samples = f32(b_, c_, s_, m) if s_ else None
-    jit_s, jit_q = f32(b_, c_), f32(b_, c_)
-    info_s, info_q = (torch.empty((b_, c_), device=dev, dtype=torch.int32) for _ in range(2))
+    mu = _f32(dev, b_, c_, m)
+    cov = _f32(dev, b_, c_, m, m) if want_cov else None
+    chol = _f32(dev, b_, c_, m, m) if want_chol else None
+    logp, lpd = (_f32(dev, b_, c_), _f32(dev, b_, c_)) if yq is not None else (None, None)
+    samples = _f32(dev, b_, c_, s_, m) if s_ else None
+    jit_s, jit_q, info_s, info_q = _f32(dev, b_, c_), _f32(dev, b_, c_), _i32(dev, b_, c_), _i32(dev, b_, c_)
     lib = _lib.load_post()
     ws_bytes = int(lib.dkt_posterior_workspace_bytes(b_, c_, m, 1 if want_cov else 0))
-    ws = torch.empty((ws_bytes // 4,), device=dev, dtype=torch.float32) if ws_bytes else None
-    strides = lambda t, size: ((c_ if t.dim() == 4 else 1) * size, size if t.dim() == 4 else 0)      # noqa: E731
+    ws = _workspace(ws_bytes, dev)
     with _timed("dkt_posterior_f32"):
-        st = lib.dkt_posterior_f32(_p(e_ss), *strides(e_ss, n * n), _p(e_qs), *strides(e_qs, m * n), _p(e_qq), *strides(e_qq, m * m), _p(y),
-                                   c_ * n if y.dim() == 3 else 0, _p(sv), _p(mean), _p(noise), _p(yq), _p(eps), b_, c_, n, m, s_, 1 if with_noise else 0,
+        st = lib.dkt_posterior_f32(_p(pr.base), *pr.base_strides, _p(e_qs), *_class_strides(e_qs, c_), _p(e_qq), *_class_strides(e_qq, c_), _p(pr.y),
+                                   pr.y_bstride, _p(sv), _p(mean), _p(noise), _p(yq), _p(eps), b_, c_, n, m, s_, 1 if with_noise else 0,
                                    float(jitter0), int(max_tries), _p(mu), _p(cov), _p(chol), _p(logp), _p(lpd), _p(samples), _p(jit_s), _p(jit_q),
                                    _p(info_s), _p(info_q), _p(ws), ws_bytes, _stream())
     _lib.check(st, "dkt_posterior_f32")
@@ -1119,17 +1122,12 @@ def _zeros_cached(c: int, dev) -> torch.Tensor:
     return t
 
 
-def _lowrank_forward(z, y, sv_, mean_, noise_in, cw_, jitter0, max_tries, unit_rows) -> dict:
-    """The forward calls of the feature-space episode on contiguous tensors (no autograd): noise floor -> A, P -> the D x D models -> alpha, logp, gradients.
+def _lowrank_forward(z, y, sv, mean, noise, cls_weight, jitter0, max_tries, unit_rows) -> dict:
+    """The forward calls of the feature-space episode (no autograd): noise floor -> A, P -> the D x D models -> alpha, logp, gradients.
     Returns obj, logp, alpha, info, jitter (total), v / t / wd (for the backward), dsv, dmean, dnoise."""
-    b_, n, d = z.shape
-    if y.dim() == 2:
-        c_, y_bstride = y.shape[0], 0
-    elif y.dim() == 3 and y.shape[0] == b_:
-        c_, y_bstride = y.shape[1], y.shape[1] * n
-    else:
-        raise RuntimeError("episode_loss_linear: y must be [C,N] or [B,C,N]")
-    dev = z.device
+    pr = _problem("episode_loss_linear", y, rows=z, sv=sv, mean=mean, noise=noise, cls_weight=cls_weight)
+    z, y, (sv_, mean_, noise_in, cw_) = pr.rows, pr.y, pr.hypers
+    b_, c_, n, d, y_bstride, dev = pr.b, pr.c, pr.n, pr.d, pr.y_bstride, pr.dev
     lib = _lib_now()
     # the rung of the jitter ladder that lifts the noise floor of the (rank-deficient) N x N matrix above fp32 rounding -- 0 for any sane noise; rows that
     # went through F.normalize have |z_i|^2 = 1, otherwise one reduction over Z finds the largest diagonal element of Z Z^T.  NOTE (ADVICE round 5): that
@@ -1141,8 +1139,7 @@ def _lowrank_forward(z, y, sv_, mean_, noise_in, cw_, jitter0, max_tries, unit_r
     pre = torch.empty_like(noise_in)
     _lib.check(lib.dkt_lowrank_noise_floor_f32(_p(sv_), _p(noise_in), _p(zmax2), float(jitter0), int(max_tries), _p(noise_), _p(pre), c_, _stream()),
                "dkt_lowrank_noise_floor_f32")
-    a = torch.empty((b_, LOWRANK_DP, LOWRANK_DP), device=dev, dtype=torch.float32)
-    p = torch.empty((b_, c_, LOWRANK_DP), device=dev, dtype=torch.float32)
+    a, p = _f32(dev, b_, LOWRANK_DP, LOWRANK_DP), _f32(dev, b_, c_, LOWRANK_DP)
     with _timed("dkt_lowrank_gram_f32"):
         st = lib.dkt_lowrank_gram_f32(_p(z), _p(y), y_bstride, _p(mean_), _p(a), _p(p), b_, c_, n, d, _stream())
     _lib.check(st, "dkt_lowrank_gram_f32")
@@ -1152,14 +1149,8 @@ def _lowrank_forward(z, y, sv_, mean_, noise_in, cw_, jitter0, max_tries, unit_r
     # float64 are logp 2.7e-5 (limit 1e-4), alpha 3.3e-5 (5e-4), dZ 4.1e-5 (1e-3) -- tests/test_lowrank_gpu.py, the table of DESIGN.md 4.6; rows without the
     # promise keep the guard
     out = mll(a, p, sv_, _zeros_cached(c_, dev), noise_, want_grad=True, cls_weight=cw_, jitter0=jitter0, max_tries=max_tries, no_kappa_guard=bool(unit_rows))
-    logp = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    alpha = torch.empty((b_, c_, n), device=dev, dtype=torch.float32)
-    v = torch.empty((b_, c_, n), device=dev, dtype=torch.float32)
-    dsv = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    dmean = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    dnoise = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    jit = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    obj = torch.empty((b_,), device=dev, dtype=torch.float32)
+    logp, alpha, v = _f32(dev, b_, c_), _f32(dev, b_, c_, n), _f32(dev, b_, c_, n)
+    dsv, dmean, dnoise, jit, obj = _f32(dev, b_, c_), _f32(dev, b_, c_), _f32(dev, b_, c_), _f32(dev, b_, c_), _f32(dev, b_)
     with _timed("dkt_lowrank_finish_f32"):
         st = lib.dkt_lowrank_finish_f32(_p(z), _p(y), y_bstride, _p(sv_), _p(mean_), _p(noise_), _p(cw_), _p(out["alpha"]), _p(out["logp"]), _p(out["dnoise"]),
                                         _p(out["jitter"]), _p(pre), _p(jit), _p(obj), _p(logp), _p(alpha), _p(v), _p(dsv), _p(dmean), _p(dnoise), b_, c_, n, d, _stream())
@@ -1196,42 +1187,21 @@ def rownoise_lowrank_applies(n: int, d: int, c: int, on_gpu: bool = True) -> boo
     return mode == "force" or n > _lib.LAPLACE_MAX_N
 
 
-def _rownoise_lowrank_args(z, y, noise_rows, sv, mean, cls_weight, what):
-    z = _req(z, "z", 3)
-    b_, n, d = z.shape
-    y = _req(y, "y", y.dim() if y.dim() in (2, 3) else 2)
-    noise_rows = _req(noise_rows, "noise_rows", noise_rows.dim() if noise_rows.dim() in (2, 3) else 2)
-    c_ = y.shape[-2]
-    if (y.shape[-1] != n or tuple(noise_rows.shape[-2:]) != (c_, n) or (y.dim() == 3 and y.shape[0] != b_)
-            or (noise_rows.dim() == 3 and noise_rows.shape[0] != b_)):
-        raise RuntimeError("%s: z must be [B,N,D] and y, noise_rows [C,N] or [B,C,N], got %s, %s and %s"
-                           % (what, tuple(z.shape), tuple(y.shape), tuple(noise_rows.shape)))
-    sv = _req(sv.reshape(-1), "sv", 1)
-    mean = _req(mean.reshape(-1), "mean", 1)
-    cw = None if cls_weight is None else _req(cls_weight.reshape(-1), "cls_weight", 1)
-    if not (sv.numel() == mean.numel() == c_) or (cw is not None and cw.numel() != c_):
-        raise RuntimeError("%s: sv / mean / cls_weight must have C=%d elements" % (what, c_))
-    return z, y, noise_rows, sv, mean, cw, (b_, c_, n, d)
-
-
 def rownoise_lowrank(z: torch.Tensor, y: torch.Tensor, noise_rows: torch.Tensor, sv: torch.Tensor, mean: torch.Tensor,
                      cls_weight: Optional[torch.Tensor] = None, want_grad: bool = False) -> dict:
     """`mll_rownoise` for the linear kernels on the rows themselves, K_c = sv_c Z Z^T + diag(noise_rows_c) (dkt_rownoise_lowrank_f32; D <= 64, any N: no
     N x N matrix exists).  z: [B,N,D]; y, noise_rows: [C,N] or [B,C,N]; sv, mean: C elements.
     Returns dict(logp [B,C] unweighted, alpha [B,C,N], info [B,C] int32, state (opaque: what `rownoise_lowrank_bwd` / `rownoise_lowrank_predict` read), and
     with want_grad dsv = cls_weight_c d logp / d sv_c, dmean = cls_weight_c sum alpha [B,C])."""
-    z, y, noise_rows, sv, mean, cw, (b_, c_, n, d) = _rownoise_lowrank_args(z, y, noise_rows, sv, mean, cls_weight, "rownoise_lowrank")
-    dev = z.device
-    logp = torch.empty((b_, c_), device=dev, dtype=torch.float32)
-    alpha = torch.empty((b_, c_, n), device=dev, dtype=torch.float32)
-    info = torch.empty((b_, c_), device=dev, dtype=torch.int32)
-    state = torch.empty((b_, c_, ROWNOISE_LOWRANK_STATE), device=dev, dtype=torch.float32)
-    dsv = torch.empty((b_, c_), device=dev, dtype=torch.float32) if want_grad else None
-    dmean = torch.empty((b_, c_), device=dev, dtype=torch.float32) if want_grad else None
+    pr = _problem("rownoise_lowrank", y, rows=z, noise_rows=noise_rows, sv=sv, mean=mean, cls_weight=cls_weight)
+    (sv, mean, cw), b_, c_, n, dev = pr.hypers, pr.b, pr.c, pr.n, pr.dev
+    logp, alpha, info, state = _f32(dev, b_, c_), _f32(dev, b_, c_, n), _i32(dev, b_, c_), _f32(dev, b_, c_, ROWNOISE_LOWRANK_STATE)
+    dsv = _f32(dev, b_, c_) if want_grad else None
+    dmean = _f32(dev, b_, c_) if want_grad else None
     with _timed("dkt_rownoise_lowrank_f32"):
-        st = _lib_now().dkt_rownoise_lowrank_f32(_p(z), _p(y), c_ * n if y.dim() == 3 else 0, _p(noise_rows), c_ * n if noise_rows.dim() == 3 else 0, _p(sv),
+        st = _lib_now().dkt_rownoise_lowrank_f32(_p(pr.rows), _p(pr.y), pr.y_bstride, _p(pr.noise_rows), pr.nr_bstride, _p(sv),
                                                  _p(mean), _p(cw), _p(logp), _p(alpha), _p(info), _p(dsv), _p(dmean), _p(state), state.numel() * 4,
-                                                 b_, c_, n, d, _stream())
+                                                 b_, c_, n, pr.d, _stream())
     _lib.check(st, "dkt_rownoise_lowrank_f32")
     return dict(logp=logp, alpha=alpha, info=info, state=state, dsv=dsv, dmean=dmean)
 
@@ -1239,15 +1209,16 @@ def rownoise_lowrank(z: torch.Tensor, y: torch.Tensor, noise_rows: torch.Tensor,
 def rownoise_lowrank_bwd(z, y, noise_rows, sv, mean, cls_weight, state: torch.Tensor, gobj: torch.Tensor) -> torch.Tensor:
     """dZ [B,N,D] of sum_b gobj[b] sum_c cls_weight[c] logp[b,c] from the state `rownoise_lowrank` left (dkt_rownoise_lowrank_bwd_f32: the classes in
     index order, no atomics)."""
-    z, y, noise_rows, sv, mean, cw, (b_, c_, n, d) = _rownoise_lowrank_args(z, y, noise_rows, sv, mean, cls_weight, "rownoise_lowrank_bwd")
+    pr = _problem("rownoise_lowrank_bwd", y, rows=z, noise_rows=noise_rows, sv=sv, mean=mean, cls_weight=cls_weight)
+    (sv, mean, cw), b_, c_ = pr.hypers, pr.b, pr.c
     state = _req(state, "state", 3)
     gobj = _req(gobj.reshape(-1), "gobj", 1)
     if tuple(state.shape) != (b_, c_, ROWNOISE_LOWRANK_STATE) or gobj.numel() != b_:
         raise RuntimeError("rownoise_lowrank_bwd: state must be the [%d,%d,%d] of rownoise_lowrank and gobj [%d]" % (b_, c_, ROWNOISE_LOWRANK_STATE, b_))
-    dz = torch.empty_like(z)
+    dz = torch.empty_like(pr.rows)
     with _timed("dkt_rownoise_lowrank_bwd_f32"):
-        st = _lib_now().dkt_rownoise_lowrank_bwd_f32(_p(z), _p(y), c_ * n if y.dim() == 3 else 0, _p(noise_rows), c_ * n if noise_rows.dim() == 3 else 0,
-                                                     _p(sv), _p(mean), _p(cw), _p(state), state.numel() * 4, _p(gobj), _p(dz), b_, c_, n, d, _stream())
+        st = _lib_now().dkt_rownoise_lowrank_bwd_f32(_p(pr.rows), _p(pr.y), pr.y_bstride, _p(pr.noise_rows), pr.nr_bstride,
+                                                     _p(sv), _p(mean), _p(cw), _p(state), state.numel() * 4, _p(gobj), _p(dz), b_, c_, pr.n, pr.d, _stream())
     _lib.check(st, "dkt_rownoise_lowrank_bwd_f32")
     return dz
 
@@ -1259,14 +1230,10 @@ def rownoise_lowrank_predict(zq: torch.Tensor, state: torch.Tensor, sv: torch.Te
     state = _req(state, "state", 3)
     b_, m, d = zq.shape
     c_ = state.shape[1]
-    sv = _req(sv.reshape(-1), "sv", 1)
-    mean = _req(mean.reshape(-1), "mean", 1)
-    if state.shape[0] != b_ or state.shape[2] != ROWNOISE_LOWRANK_STATE or not (sv.numel() == mean.numel() == c_):
-        raise RuntimeError("rownoise_lowrank_predict: state must be the [B=%d,C,%d] of rownoise_lowrank and sv, mean have C elements, got %s, %d and %d"
-                           % (b_, ROWNOISE_LOWRANK_STATE, tuple(state.shape), sv.numel(), mean.numel()))
-    mu = torch.empty((b_, c_, m), device=zq.device, dtype=torch.float32)
-    var = torch.empty((b_, c_, m), device=zq.device, dtype=torch.float32)
-    labels = torch.empty((b_, m), device=zq.device, dtype=torch.int32)
+    if state.shape[0] != b_ or state.shape[2] != ROWNOISE_LOWRANK_STATE:
+        raise RuntimeError("rownoise_lowrank_predict: state must be the [B=%d,C,%d] of rownoise_lowrank, got %s" % (b_, ROWNOISE_LOWRANK_STATE, tuple(state.shape)))
+    sv, mean = _hypers("rownoise_lowrank_predict", c_, dict(sv=sv, mean=mean))
+    mu, var, labels = _f32(zq.device, b_, c_, m), _f32(zq.device, b_, c_, m), _i32(zq.device, b_, m)
     with _timed("dkt_rownoise_lowrank_predict_f32"):
         st = _lib_now().dkt_rownoise_lowrank_predict_f32(_p(zq), _p(state), state.numel() * 4, _p(sv), _p(mean), _p(mu), _p(var), _p(labels), b_, c_, m, d,
                                                          _stream())
@@ -1375,7 +1342,7 @@ def bn_param_grads(dg: torch.Tensor, db: torch.Tensor):
     og = torch.empty((d,), device=dg.device, dtype=torch.float32)
     ob = torch.empty((d,), device=dg.device, dtype=torch.float32)
     ws_bytes = int(lib.dkt_bn_param_grads_workspace_bytes(b_, d))
-    ws = torch.empty((ws_bytes + 3) // 4, device=dg.device, dtype=torch.float32) if ws_bytes else None
+    ws = _workspace(ws_bytes, dg.device)
     with _timed("dkt_bn_param_grads_f32"):
         st = lib.dkt_bn_param_grads_f32(_p(dg), _p(db), _p(og), _p(ob), b_, d, _p(ws), ws_bytes, _stream())
     _lib.check(st, "dkt_bn_param_grads_f32")
@@ -1511,10 +1478,8 @@ class _FeatureSpaceGaussian(_Gaussian):
     @staticmethod
     def forward(rows, y, sv, mean, noise, cls_weight, jitter0, max_tries):
         z, unit_rows = rows
-        cw_ = _req(cls_weight.reshape(-1), "cls_weight", 1)
-        o = _lowrank_forward(z, _req(y, "y"), _req(sv.reshape(-1), "sv", 1), _req(mean.reshape(-1), "mean", 1), _req(noise.reshape(-1), "noise", 1), cw_,
-                             jitter0, max_tries, unit_rows)
-        return (o["obj"], (o["logp"], o["alpha"], o["info"], o["jitter"]), (o["v"], o["t"], o["wd"], o["dsv"], o["dmean"], o["dnoise"], cw_),
+        o = _lowrank_forward(z, y, sv, mean, noise, cls_weight, jitter0, max_tries, unit_rows)           # (normalises them: `_problem`)
+        return (o["obj"], (o["logp"], o["alpha"], o["info"], o["jitter"]), (o["v"], o["t"], o["wd"], o["dsv"], o["dmean"], o["dnoise"], cls_weight),
                 (sv.shape, mean.shape, noise.shape))
 
     @staticmethod
@@ -1581,8 +1546,7 @@ class _FeatureSpaceDirichlet(_Dirichlet):
         with torch.no_grad():
             out = rownoise_lowrank(z, ytilde, noise_rows, sv, mean, cls_weight, want_grad=True)
             obj = objective(out["logp"], cls_weight)
-            kept = (ytilde.contiguous(), noise_rows.contiguous(), sv.reshape(-1).contiguous(), mean.reshape(-1).contiguous(),
-                    None if cls_weight is None else cls_weight.reshape(-1).contiguous())
+        kept = (ytilde, noise_rows, sv, mean, cls_weight)                         # (as given: `rownoise_lowrank_bwd` normalises them as `rownoise_lowrank` did)
         return obj, (out["logp"], out["alpha"], out["info"]), (out["state"], out["dsv"], out["dmean"]) + kept, (sv.shape, mean.shape)
 
     @staticmethod
