@@ -133,6 +133,14 @@ def _class_cut(s, y, *per_class):
     return (y[..., s, :].contiguous(),) + tuple(None if t is None else t[s] for t in per_class)
 
 
+def first_argmax(mu, dim, dtype=torch.int64):
+    """The arg-max of mu along dim as `dtype`; the first maximum wins, as np.argmax (torch.argmax does not promise which of several equal maxima it returns
+    on the GPU)."""
+    n = mu.shape[dim]
+    idx = torch.arange(n, device=mu.device, dtype=dtype).view([n if k == dim % mu.dim() else 1 for k in range(mu.dim())])
+    return torch.where(mu == mu.max(dim, keepdim=True).values, idx, torch.full_like(idx, n)).min(dim).values
+
+
 class _FusableBatchNorm1d(nn.BatchNorm1d):
     """bn_out (DKT.py:48) with the same parameters / buffers / state-dict keys as nn.BatchNorm1d; `bypass` lets the fused
     front end (ops.episode_loss_bn) take the trunk output in front of it and run the normalisation inside the Gram kernels."""
@@ -390,6 +398,39 @@ class DKT(MetaTemplate):
         """The {0,1} form of the +-1 one-vs-rest targets."""
         return ((y + 1.0) * 0.5).contiguous()
 
+    def _objective(self, rows, y):
+        """What the model's (likelihood_type, objective_type) minimises on episodes of rows [B,N,D] (features, or the trunk output in front of the fused front
+        end: their shape and device are read) with +-1 targets y [C,N], stated ONCE for both losses: the limits of its kernels, checked on the host before any
+        launch, then its name in ops.OBJECTIVES and its arguments, the transformed targets first.  Every one is -(1/C) sum_c logp_c / N through the class
+        weights (the reference's SumMarginalLogLikelihood / ExactMarginalLogLikelihood scaling, DKT.py:160-163)."""
+        n, c = rows.shape[1], y.shape[-2]
+        sv, mean, noise = self._hypers()
+        cw = torch.full((c,), -1.0 / (c * n), device=rows.device, dtype=torch.float32)
+        if self.likelihood_type == "bernoulli":
+            # the Laplace approximation: the Gaussian noise and the constant mean do not enter this model and receive no gradient
+            self._check_resident_rows(n, c)
+            return "laplace", (self._bernoulli_targets(y), sv, cw, ops.LAPLACE_MAX_ITER)
+        if self.likelihood_type == "dirichlet":
+            # the C = n_way exact GPs on the transformed labels: outputscale and the constant mean train, the noise is the likelihood's own per row and the
+            # frozen Gaussian noise does not enter
+            if not self._dirichlet_in_feature_space(rows, c):
+                self._check_resident_rows(n, c, "dirichlet")
+            return "dirichlet", self._dirichlet_targets(y) + (sv, mean, cw)
+        if self.objective_type == "loo":
+            self._loo_in_feature_space(rows, c)             # (raises where neither the feature-space route nor the resident kernel takes the episode)
+        return ("loo" if self.objective_type == "loo" else "gaussian"), (y, sv, mean, noise, cw, self.jitter0, self.max_tries)
+
+    @staticmethod
+    def _aux(out):
+        """`aux` of a loss from the named outputs of its episode call: logp, alpha, info, jitter and e (detached; None in feature space) under every objective,
+        None where it has none, and what it has beyond them (iters; mu_loo, var_loo)."""
+        aux = {k: out.get(k) for k in ("logp", "alpha", "info", "jitter")}
+        if aux["info"] is None:                               # (Laplace: B = I + W^1/2 K W^1/2 has eigenvalues >= 1: no jitter ladder, nothing can fail)
+            aux["info"] = torch.zeros_like(out["iters"])
+        aux["e"] = None if out["e"] is None else out["e"].detach()
+        aux.update((k, out[k]) for k in ("iters", "mu_loo", "var_loo") if k in out)
+        return aux
+
     def _check_way(self, n_way):
         if n_way != self.model.n_models:
             raise RuntimeError("DKT was built with %d GP models but the episode has %d classes "
@@ -462,46 +503,18 @@ class DKT(MetaTemplate):
         Returns (loss, aux, z_train) with z_train the normalised train-mode features (detached) of the first episode, which
         the in-loop evaluation conditions on (DKT.py:170-192)."""
         xb = (x_feat if x_feat.dim() == 3 else x_feat.unsqueeze(0)).contiguous()
-        n = xb.shape[1]
-        c = y.shape[-2]
-        sv, mean, noise = self._hypers()
-        cw = torch.full((c,), -1.0 / (c * n), device=xb.device, dtype=torch.float32)
-        bn = self._bn_out(True)
-        if self.likelihood_type == "bernoulli":
-            self._check_resident_rows(n, c)
-            obj, logp, iters, e, bmean, bvar, a, s, rnorm = ops.episode_loss_laplace_bn(
-                xb, None if bn is None else bn.weight, None if bn is None else bn.bias, self._bernoulli_targets(y), sv, cw,
-                eps=1e-5 if bn is None else bn.eps, use_bn=bn is not None)
-            alpha, jit, info = None, None, torch.zeros_like(iters)      # (B = I + W^1/2 K W^1/2 has eigenvalues >= 1: no jitter ladder, nothing can fail)
-        elif self.likelihood_type == "dirichlet":
-            if not self._dirichlet_in_feature_space(xb, c):
-                self._check_resident_rows(n, c, "dirichlet")
-            yt, nr = self._dirichlet_targets(y)
-            obj, logp, alpha, info, e, bmean, bvar, a, s, rnorm = ops.episode_loss_dirichlet_bn(
-                xb, None if bn is None else bn.weight, None if bn is None else bn.bias, yt, nr, sv, mean, cw,
-                eps=1e-5 if bn is None else bn.eps, use_bn=bn is not None)
-            jit = None
-        elif self.objective_type == "loo":
-            self._loo_in_feature_space(xb, c)             # (raises where neither the feature-space route nor the resident kernel takes the episode)
-            obj, logp, alpha, info, jit, mu_loo, var_loo, e, bmean, bvar, a, s, rnorm = ops.episode_loss_loo_bn(
-                xb, None if bn is None else bn.weight, None if bn is None else bn.bias, y, sv, mean, noise, cw,
-                eps=1e-5 if bn is None else bn.eps, jitter0=self.jitter0, max_tries=self.max_tries, use_bn=bn is not None)
-        else:
-            if bn is not None:
-                outs = ops.episode_loss_bn(xb, bn.weight, bn.bias, y, sv, mean, noise, cw, eps=bn.eps, jitter0=self.jitter0,
-                                           max_tries=self.max_tries, use_bn=True, full=True)
-            else:
-                outs = ops.episode_loss_bn(xb, None, None, y, sv, mean, noise, cw, jitter0=self.jitter0, max_tries=self.max_tries,
-                                           use_bn=False, full=True)
-            obj, logp, alpha, info, jit, e, bmean, bvar, a, s, rnorm = outs
+        name, oargs = self._objective(xb, y)
+        bn = self._bn_out(True)                                   # the front end's (x, gamma, beta, eps, use_bn)
+        fargs = (xb, None, None, 1e-5, False) if bn is None else (xb, bn.weight, bn.bias, bn.eps, True)
+        out = dict(zip(("obj",) + ops.OBJECTIVE_OUTPUTS[name] + ops.BN_TRUNK_OUTPUTS, ops._episode(ops._BnTrunk, fargs, name, oargs)))
         with torch.no_grad():
             if bn is not None and bn.track_running_stats:
-                self._update_running_stats(bn, bmean, bvar)
+                self._update_running_stats(bn, out["batch_mean"], out["batch_var_unbiased"])
             z_train = None
             if want_z:
-                z_train = (xb[0].detach() * a.reshape(-1, xb.shape[2])[0] + s.reshape(-1, xb.shape[2])[0]) * rnorm[0].unsqueeze(1)
-        aux = dict(logp=logp, alpha=alpha, info=info, jitter=jit, e=None if e is None else e.detach())
-        return obj.mean(), aux, z_train
+                d = xb.shape[2]
+                z_train = (xb[0].detach() * out["a"].reshape(-1, d)[0] + out["s"].reshape(-1, d)[0]) * out["rnorm"][0].unsqueeze(1)
+        return out["obj"].mean(), self._aux(out), z_train
 
     @staticmethod
     def _update_running_stats(bn, bmean, bvar):
@@ -529,43 +542,16 @@ class DKT(MetaTemplate):
     def _episode_loss(self, z, y):
         """loss = -(1/C) sum_c logp_c / N for ONE episode z:[N,D] (or a batch [B,N,D] -> mean over B)."""
         zb = z if z.dim() == 3 else z.unsqueeze(0)
-        n = zb.shape[1]
-        c = y.shape[-2]
-        sv, mean, noise = self._hypers()
-        cw = torch.full((c,), -1.0 / (c * n), device=zb.device, dtype=torch.float32)
-        if self.likelihood_type == "bernoulli":
-            # minimise -(1/C) sum_c lml_c / N of the Laplace approximation (the reference's SumMarginalLogLikelihood / ExactMarginalLogLikelihood scaling,
-            # DKT.py:160-163); the Gaussian noise and the constant mean do not enter this model and receive no gradient
-            self._check_resident_rows(n, c)
-            obj, logp, iters, e = ops.episode_loss_laplace(zb, self._bernoulli_targets(y), sv, cw, self.kernel_type, self.model.lengthscale, self.model.offset,
-                                                           unit_rows=bool(self.normalize))
-            aux = dict(logp=logp, alpha=None, info=torch.zeros_like(iters), jitter=None, e=e.detach(), iters=iters)
-            return obj.mean(), aux
-        if self.likelihood_type == "dirichlet":
-            # minimise -(1/C) sum_c logp_c / N of the C = n_way exact GPs on the transformed labels (the same scaling); outputscale and the constant mean train, the
-            # noise is the likelihood's own per row and the frozen Gaussian noise does not enter
-            if not self._dirichlet_in_feature_space(zb, c):
-                self._check_resident_rows(n, c, "dirichlet")
-            yt, nr = self._dirichlet_targets(y)
-            obj, logp, alpha, info, e = ops.episode_loss_dirichlet(zb, yt, nr, sv, mean, cw, self.kernel_type, self.model.lengthscale, self.model.offset,
-                                                                   unit_rows=bool(self.normalize))
-            return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=None, e=None if e is None else e.detach())      # (no E in feature space)
-        if self.objective_type == "loo":
-            # minimise -(1/C) sum_c loo_c / N: the same scaling and class weights as the marginal likelihood below, every kernel through E (one launch over all
-            # (episode, class) matrices) -- or, the linear kernels above 128 rows, on the rows themselves (no E)
-            self._loo_in_feature_space(zb, c)
-            obj, logp, alpha, info, jit, mu_loo, var_loo, e = ops.episode_loss_loo(zb, y, sv, mean, noise, cw, self.kernel_type, self.model.lengthscale,
-                                                                                   self.model.offset, unit_rows=bool(self.normalize), jitter0=self.jitter0,
-                                                                                   max_tries=self.max_tries)
-            return obj.mean(), dict(logp=logp, alpha=alpha, info=info, jitter=jit, e=None if e is None else e.detach(), mu_loo=mu_loo, var_loo=var_loo)
-        if self.kernel_type in LINEAR_KINDS:
-            obj, logp, alpha, info, jit, e = ops.episode_loss_linear(zb, y, sv, mean, noise, cw, self.jitter0, self.max_tries,
-                                                                     unit_rows=bool(self.normalize))
+        name, oargs = self._objective(zb, y)
+        ls, off = self.model.lengthscale, self.model.offset
+        if name != "gaussian" or self.kernel_type in LINEAR_KINDS:
+            # every kernel through E, one launch over all (episode, class) matrices -- or, the linear kernels where the objective says so, on the rows (no E)
+            parts = [ops._episode(*ops._rows_front(zb, self.kernel_type, ls, off, bool(self.normalize)), name, oargs)]
         else:
             # rbf / matern / polynomial: every class model owns its lengthscale / offset (one ExactGPLayer per class,
             # DKT.py:63-66), so the base matrix differs per class
-            ls, off = self.model.lengthscale, self.model.offset
-            groups, class_form = _class_plan(n, c)
+            y, sv, mean, noise, cw, _, _ = oargs
+            groups, class_form = _class_plan(zb.shape[1], y.shape[-2])
             parts = []
             for s in groups:
                 yk, svk, meank, noisek, cwk, lsk, offk = _class_cut(s, y, sv, mean, noise, cw, ls, off)
@@ -576,14 +562,23 @@ class DKT(MetaTemplate):
                 else:       # (E of a single model is not kept: nothing reads it)
                     parts.append(ops.mll_objective(ops.base_matrix(zb, self.kernel_type, lsk, offk), yk, svk, meank, noisek, cwk,
                                                    self.jitter0, self.max_tries) + (None,))
-            if len(parts) == 1:
-                obj, logp, alpha, info, jit, e = parts[0]
-            else:           # the class weights already carry 1 / (C N), so the parts' objectives add up
-                obj = torch.stack([pt[0] for pt in parts], 0).sum(0)
-                logp, alpha, info, jit = (torch.cat([pt[i] for pt in parts], 1) for i in range(1, 5))
-                e = torch.cat([pt[5] for pt in parts], 1) if class_form else None
-        aux = dict(logp=logp, alpha=alpha, info=info, jitter=jit, e=None if e is None else e.detach())
-        return obj.mean(), aux
+            if len(parts) > 1:           # the class weights already carry 1 / (C N), so the parts' objectives add up
+                parts = [(torch.stack([pt[0] for pt in parts], 0).sum(0),) + tuple(torch.cat([pt[i] for pt in parts], 1) for i in range(1, 5))
+                         + (torch.cat([pt[5] for pt in parts], 1) if class_form else None,)]
+        out = dict(zip(("obj",) + ops.OBJECTIVE_OUTPUTS[name] + ops.ROWS_OUTPUTS, parts[0]))
+        return out["obj"].mean(), self._aux(out)
+
+    def _kernel_matrices(self, parts, zc, zq=None, ls=None, off=None, class_form=True):
+        """The model's base kernel matrices (no autograd) of a conditioning set zc [B,N,D] and queries zq [B,M,D], the ONE statement of their rule: the linear
+        kinds share ops.kernel_matrix [B,.,.], every other kernel has one matrix per class model with its own lengthscale / offset (ops.kernel_matrix_per_class
+        [B,C,.,.]; class_form=False: the single model's), and the query diagonal is |zq|^2 or the diagonal of a third per-class call.  parts: which of "e" =
+        k(zc, zc), "x" = k(zq, zc), "d" = diag k(zq, zq), one letter each: made in that order (a caller's launches stay where they were) and returned in it."""
+        linear = self.kernel_type in LINEAR_KINDS
+        kmat = ops.kernel_matrix if linear or not class_form else ops.kernel_matrix_per_class
+        make = dict(e=lambda: kmat(zc, None, self.kernel_type, ls, off), x=lambda: kmat(zq, zc, self.kernel_type, ls, off),
+                    d=lambda: (zq * zq).sum(-1) if linear else torch.diagonal(kmat(zq, None, self.kernel_type, ls, off), dim1=-2, dim2=-1))
+        out = tuple(make[p]() for p in parts)
+        return out[0] if len(out) == 1 else out
 
     @gp_head
     def _posterior(self, z_cond, y, z_star, e_cond=None):
@@ -597,29 +592,25 @@ class DKT(MetaTemplate):
             return mu[0], labels[0], out
         if self.kernel_type in LINEAR_KINDS:
             if e_cond is None:
-                e_cond = ops.kernel_matrix(zc, None, self.kernel_type)
+                e_cond = self._kernel_matrices("e", zc)
             out = self._condition(e_cond, y, sv, mean, noise)
-            mu, labels = ops.predict(ops.kernel_matrix(zs, zc, self.kernel_type), out["alpha"], sv, mean)
+            mu, labels = ops.predict(self._kernel_matrices("x", zc, zs), out["alpha"], sv, mean)
             return mu[0], labels[0], out
         # per-class base matrices (E depends on the class model's own, post-step, lengthscale / offset)
         # class-kernel form: one contraction for the conditioning set, one for the cross kernel, the class maps element-wise ([1, C, N, N], [1, C, M, N]), one
         # marginal-likelihood launch and one dkt_predict_per_class_f32 launch per class slice; single-model form: the same four calls per class
         groups, class_form = _class_plan(zc.shape[1], y.shape[-2])
-        kmat = ops.kernel_matrix_per_class if class_form else ops.kernel_matrix
         mus, outs = [], []
         for s in groups:
             yk, svk, meank, noisek, lsk, offk = _class_cut(s, y, sv, mean, noise, ls, off)
-            o = self._condition(kmat(zc, None, self.kernel_type, lsk, offk), yk, svk, meank, noisek)
-            m, labels = ops.predict(kmat(zs, zc, self.kernel_type, lsk, offk), o["alpha"], svk, meank, want_labels=len(groups) == 1)
+            o = self._condition(self._kernel_matrices("e", zc, None, lsk, offk, class_form), yk, svk, meank, noisek)
+            m, labels = ops.predict(self._kernel_matrices("x", zc, zs, lsk, offk, class_form), o["alpha"], svk, meank, want_labels=len(groups) == 1)
             mus.append(m); outs.append(o)
         if len(groups) == 1:                                 # (the labels come from the predict kernel)
             return m[0], labels[0], {key: o[key] for key in ("logp", "alpha", "jitter", "info")}
         mu = torch.cat(mus, 1)
         out = {key: torch.cat([o[key] for o in outs], 1) for key in ("logp", "alpha", "jitter", "info")}
-        # first maximum wins, as np.argmax (torch.argmax does not promise which of several equal maxima it returns on the GPU)
-        cidx = torch.arange(mu.shape[1], device=mu.device, dtype=torch.int32).view(1, -1, 1)
-        labels = torch.where(mu == mu.max(1, keepdim=True).values, cidx, torch.full_like(cidx, mu.shape[1])).min(1).values
-        return mu[0], labels[0], out
+        return mu[0], first_argmax(mu, 1, torch.int32)[0], out
 
     def _posterior_fused_eval(self, x_support, x_query, y):
         """Test-time episode with bn_out (eval mode: running statistics) + F.normalize folded into ONE Gram launch over the
@@ -880,14 +871,17 @@ class DKT(MetaTemplate):
         pick = slice(1, 2) if self.n_way == 2 else slice(None)
         sv, _, _, ls, off = self._hypers_detached()
         sv = sv[pick]
-        if self.kernel_type in LINEAR_KINDS:
-            e, ex = ops.kernel_matrix(zs, None, self.kernel_type).unsqueeze(1), ops.kernel_matrix(zq, zs, self.kernel_type).unsqueeze(1)
-            exx = (zq * zq).sum(-1).unsqueeze(1)
-        else:
-            e = ops.kernel_matrix_per_class(zs, None, self.kernel_type, ls, off)[:, pick]
-            ex = ops.kernel_matrix_per_class(zq, zs, self.kernel_type, ls, off)[:, pick]
-            exx = torch.diagonal(ops.kernel_matrix_per_class(zq, None, self.kernel_type, ls, off)[:, pick], dim1=-2, dim2=-1)
+        # (the linear kinds: one matrix for every class model; otherwise the class models picked above)
+        e, ex, exx = (t.unsqueeze(1) if self.kernel_type in LINEAR_KINDS else t[:, pick] for t in self._kernel_matrices("exd", zs, zq, ls, off))
         return sv.view(1, -1, 1, 1) * e, sv.view(1, -1, 1, 1) * ex, (sv.view(1, -1, 1) * exx).contiguous()
+
+    def _embed_episodes(self, xd):
+        """fp32 embeddings (support [B, ns, D], queries [B, nq, D]) of the episodes xd [B, n_way, n_support + n_query, ...]: one backbone pass per episode
+        over its [support; query] rows (called under torch.no_grad)."""
+        ns, nq = self.n_way * self.n_support, self.n_way * (xd.shape[2] - self.n_support)
+        z = torch.stack([self._embed(torch.cat([xe[:, :self.n_support].reshape(ns, *xe.shape[2:]), xe[:, self.n_support:].reshape(nq, *xe.shape[2:])], 0))
+                         for xe in xd], 0).detach().float()
+        return z[:, :ns].contiguous(), z[:, ns:].contiguous()
 
     def _laplace_device(self, x, kernel, batched=False):
         """An episode x [n_way, n_support + n_query, ...] (batched: B of them, [B, n_way, ...]) -> (mu, var, prob [B,C,M], labels [B,M]): one backbone
@@ -895,16 +889,14 @@ class DKT(MetaTemplate):
         matrices, then ONE mode launch and ONE predict launch for all B x C binary problems."""
         self._check_way(self.n_way)
         xd = self._upload(x if batched else x.unsqueeze(0))
-        b_, ns, nq = xd.shape[0], self.n_way * self.n_support, self.n_way * (xd.shape[2] - self.n_support)
+        ns = self.n_way * self.n_support
         if not ops.laplace_supported(ns, self.n_way):
             raise RuntimeError("Laplace GPC on the device takes up to %d support rows and %d classes, the episode has %d and %d"
                                % (ops._lib.GPC_MAX_N, ops._lib.GPC_MAX_C, ns, self.n_way))
         with torch.no_grad():
-            z = torch.stack([self._embed(torch.cat([xe[:, :self.n_support].reshape(ns, *xe.shape[2:]), xe[:, self.n_support:].reshape(nq, *xe.shape[2:])], 0))
-                             for xe in xd], 0).detach().float()
-            zs, zq = z[:, :ns].contiguous(), z[:, ns:].contiguous()
+            zs, zq = self._embed_episodes(xd)
             k, ks, kss = self._laplace_kernels(zs, zq, kernel)
-            mode = ops.laplace_mode(k, self._laplace_targets(self.n_way, self.n_support, z.device))
+            mode = ops.laplace_mode(k, self._laplace_targets(self.n_way, self.n_support, zs.device))
             self._last["laplace_mode"] = mode
             return ops.laplace_predict(ks, kss, mode)
 
@@ -922,27 +914,21 @@ class DKT(MetaTemplate):
         on the support set with the model's own kernel: (mu, var [B,C,M]).  One backbone pass per episode, as in `_laplace_device`."""
         self._check_way(self.n_way)
         xd = self._upload(x if batched else x.unsqueeze(0))
-        ns, nq = self.n_way * self.n_support, self.n_way * (xd.shape[2] - self.n_support)
         with torch.no_grad():
             self._mode(False)
-            z = torch.stack([self._embed(torch.cat([xe[:, :self.n_support].reshape(ns, *xe.shape[2:]), xe[:, self.n_support:].reshape(nq, *xe.shape[2:])], 0))
-                             for xe in xd], 0).detach().float()
-            zs, zq = z[:, :ns].contiguous(), z[:, ns:].contiguous()
+            zs, zq = self._embed_episodes(xd)
             sv, mean, _, ls, off = self._hypers_detached()
-            yt, nr = self._dirichlet_targets(self._targets(self.n_way, self.n_support, z.device))
+            yt, nr = self._dirichlet_targets(self._targets(self.n_way, self.n_support, zs.device))
             if self._dirichlet_in_feature_space(zs, self.n_way):          # (more than 127 support rows: the D x D models, the latent variance from their state)
                 out = ops.rownoise_lowrank(zs, yt, nr, sv, mean)
                 return ops.rownoise_lowrank_predict(zq, out["state"], sv, mean)[:2]
-            self._check_resident_rows(ns, self.n_way, "dirichlet", "n_way * n_support")
+            self._check_resident_rows(zs.shape[1], self.n_way, "dirichlet", "n_way * n_support")
             zero = torch.zeros_like(sv)                       # the LATENT variance: no observation noise on the queries
-            if self.kernel_type in LINEAR_KINDS:
-                ex = ops.kernel_matrix(zq, zs, self.kernel_type)
-                out = ops.mll_rownoise(ops.kernel_matrix(zs, None, self.kernel_type), yt, nr, sv, mean, want_chol=True)
-                return ops.predict(ex, out["alpha"], sv, mean, want_labels=False)[0], ops.predict_var(ex, (zq * zq).sum(-1), out["chol"], sv, zero)
-            ex = ops.kernel_matrix_per_class(zq, zs, self.kernel_type, ls, off)
-            exx = torch.diagonal(ops.kernel_matrix_per_class(zq, None, self.kernel_type, ls, off), dim1=-2, dim2=-1)
-            out = ops.mll_rownoise(ops.kernel_matrix_per_class(zs, None, self.kernel_type, ls, off), yt, nr, sv, mean, want_chol=True)
+            ex, exx, e = self._kernel_matrices("xde", zs, zq, ls, off)
+            out = ops.mll_rownoise(e, yt, nr, sv, mean, want_chol=True)
             mu = ops.predict(ex, out["alpha"], sv, mean, want_labels=False)[0]
+            if self.kernel_type in LINEAR_KINDS:
+                return mu, ops.predict_var(ex, exx, out["chol"], sv, zero)
             # (dkt_predict_var_f32 takes one cross kernel for the class models it is given: a call per class model here)
             var = torch.cat([ops.predict_var(ex[:, k].contiguous(), exx[:, k].contiguous(), out["chol"][:, k:k + 1].contiguous(), sv[k:k + 1], zero[k:k + 1])
                              for k in range(self.n_way)], 1)
@@ -973,17 +959,12 @@ class DKT(MetaTemplate):
             if self._loo_in_feature_space(zs, self.n_way, rows="n_way * n_support"):
                 out = ops.loo_lowrank(zs, y, sv, mean, noise, jitter0=self.jitter0, max_tries=self.max_tries)
             else:
-                e = (ops.kernel_matrix(zs, None, self.kernel_type) if self.kernel_type in LINEAR_KINDS
-                     else ops.kernel_matrix_per_class(zs, None, self.kernel_type, ls, off))
-                out = ops.loo(e, y, sv, mean, noise, jitter0=self.jitter0, max_tries=self.max_tries)
+                out = ops.loo(self._kernel_matrices("e", zs, None, ls, off), y, sv, mean, noise, jitter0=self.jitter0, max_tries=self.max_tries)
             self._last["loo"] = out
             if int(out["info"].abs().max().item()) != 0:
                 _not_pd("DKT.loo_accuracy")
-            mu = out["mu_loo"][0]
-            cidx = torch.arange(mu.shape[0], device=mu.device).view(-1, 1)
-            labels = torch.where(mu == mu.max(0, keepdim=True).values, cidx, torch.full_like(cidx, mu.shape[0])).min(0).values
-            y_s = torch.arange(self.n_way, device=mu.device).repeat_interleave(self.n_support)
-            return float((labels == y_s).float().mean().item() * 100.0)
+            y_s = torch.arange(self.n_way, device=zs.device).repeat_interleave(self.n_support)
+            return float((first_argmax(out["mu_loo"][0], 0) == y_s).float().mean().item() * 100.0)
 
     def correct(self, x, N=0, laplace=False):
         out = self._correct_device(x, N, laplace)

@@ -22,7 +22,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from typing import NamedTuple, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -1709,108 +1709,142 @@ class _EpisodeFn(torch.autograd.Function):
                 + objv.backward(osaved, ostatic, gobj, *need[n:]))
 
 
+class _Objective(NamedTuple):
+    on_e: type                            # the class that works on E
+    on_rows: Optional[type]               # its feature-space form (`on_features`: works on the rows, no E), or None
+    applies: Optional[Callable]           # applies(n, d, c, ...): does an episode of the linear kernels take the feature-space form?
+    outputs: tuple                        # its non-differentiable outputs, in the order `forward` returns them
+
+
+# What is solved on an episode, by name.  The first output is the log probability per (episode, class) whatever the objective calls it (the marginal
+# likelihood, the leave-one-out likelihood `loo`, the Laplace approximation `lml`).
+OBJECTIVES = {
+    "gaussian": _Objective(_Gaussian, _FeatureSpaceGaussian, lowrank_applies, ("logp", "alpha", "info", "jitter")),
+    "loo": _Objective(_LooCV, _FeatureSpaceLooCV, loo_lowrank_applies, ("logp", "alpha", "info", "jitter", "mu_loo", "var_loo")),
+    "laplace": _Objective(_Laplace, None, None, ("logp", "iters")),
+    "dirichlet": _Objective(_Dirichlet, _FeatureSpaceDirichlet, rownoise_lowrank_applies, ("logp", "alpha", "info")),
+}
+OBJECTIVE_OUTPUTS = {name: row.outputs for name, row in OBJECTIVES.items()}
+LAPLACE_MAX_ITER = 100                    # the Newton iterations the Laplace objective allows its mode search (`max_iter` of the public calls)
+# the outputs of the front ends (E is None where the episode ran in feature space): an `_EpisodeFn` result is ("obj",) + OBJECTIVE_OUTPUTS[...] + one of these
+GIVEN_E_OUTPUTS = ()
+ROWS_OUTPUTS = ("e",)                                                                   # _LinearGram, _ClassKernel
+BN_TRUNK_OUTPUTS = ("e", "batch_mean", "batch_var_unbiased", "a", "s", "rnorm")
+
+
+_ROWS_FRONTS = (_LinearGram, _BnTrunk)                # their first argument is the [B,N,D] operand a feature-space objective can take in the place of E
+
+
+def _episode(front, fargs: tuple, name: str, oargs: tuple):
+    """obj [B] and the outputs of one (front end, objective) pair: `front` with its arguments, the objective `name` of OBJECTIVES with its arguments (the
+    targets first).  The ONE place that asks the objective's `applies` whether the episode runs in feature space: the marginal likelihood draws its line by the
+    batch size and by the fused front end, the others by where the rows live."""
+    row, rows = OBJECTIVES[name], fargs[0]
+    on_rows = (row.applies is not None and front in _ROWS_FRONTS and rows.dim() == 3
+               and row.applies(rows.shape[1], rows.shape[2], oargs[0].shape[-2], *((rows.shape[0], front is _BnTrunk) if name == "gaussian" else (rows.is_cuda,))))
+    return _EpisodeFn.apply(front, row.on_rows if on_rows else row.on_e, *fargs, *oargs)
+
+
+def _rows_front(z, kernel: str, lengthscale, offset, unit_rows):
+    """(front end, its arguments) of the episodes z [B,N,D] under `kernel`: the linear Gram, or the contraction + class maps of the kernels with per-class
+    parameters."""
+    z = _req(z, "z", 3)
+    if kernel in LINEAR_KINDS:
+        return _LinearGram, (z, unit_rows)
+    cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
+    return _ClassKernel, (z, param, cmap, power, base_kind)
+
+
 def mll_objective(e, y, sv, mean, noise, cls_weight, jitter0: float = 1e-6, max_tries: int = 3):
-    """Returns (obj[B], logp[B,C], alpha[B,C,N], info[B,C], jitter[B,C])."""
-    return _EpisodeFn.apply(_GivenE, _Gaussian, e, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+    """Returns (obj, logp, alpha, info, jitter): obj [B], logp [B,C], alpha [B,C,N], info [B,C], jitter [B,C]."""
+    return _episode(_GivenE, (e,), "gaussian", (y, sv, mean, noise, cls_weight, jitter0, max_tries))
 
 
 def laplace_objective(K, Y, cls_weight, scale=None, max_iter: int = 100):
-    """Differentiable (in K and scale) Laplace training objective of B episodes: returns (obj [B], lml [B,C], iters [B,C]); arguments as `laplace_grad`.
-    Forward: `laplace_mode` without autograd, then `laplace_grad`; no host read-back (graph-capturable like the other episode calls)."""
-    return _EpisodeFn.apply(_GivenE, _Laplace, K, Y, scale, cls_weight, max_iter)
+    """Differentiable (in K and scale) Laplace training objective of B episodes; arguments as `laplace_grad`.  Returns (obj, logp, iters): obj [B], logp [B,C]
+    the approximate log marginal likelihood lml, iters [B,C].  Forward: `laplace_mode` without autograd, then `laplace_grad`; no host read-back
+    (graph-capturable like the other episode calls)."""
+    return _episode(_GivenE, (K,), "laplace", (Y, scale, cls_weight, max_iter))
 
 
 def episode_loss_laplace(z, y, sv, cls_weight, kernel: str, lengthscale=None, offset=None, unit_rows: bool = False, max_iter: int = 100):
-    """Bernoulli-likelihood training episode(s) z [B,N,D] (N <= 127, C <= 32), y in {0,1}: K_c = sv_c * k_c(z, z).  Returns (obj [B], lml [B,C], iters [B,C], E)."""
-    z = _req(z, "z", 3)
-    if kernel in LINEAR_KINDS:
-        return _EpisodeFn.apply(_LinearGram, _Laplace, z, unit_rows, y, sv, cls_weight, max_iter)
-    cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
-    return _EpisodeFn.apply(_ClassKernel, _Laplace, z, param, cmap, power, base_kind, y, sv, cls_weight, max_iter)
+    """Bernoulli-likelihood training episode(s) z [B,N,D] (N <= 127, C <= 32), y in {0,1}: K_c = sv_c * k_c(z, z).  Returns (obj, logp, iters, e): obj [B],
+    logp [B,C] (lml), iters [B,C], E."""
+    return _episode(*_rows_front(z, kernel, lengthscale, offset, unit_rows), "laplace", (y, sv, cls_weight, max_iter))
 
 
 def episode_loss_laplace_bn(x, gamma, beta, y, sv, cls_weight, eps: float = 1e-5, use_bn: bool = True, max_iter: int = 100):
-    """x [B,N,D] trunk output BEFORE bn_out, N <= 127.  Returns (obj [B], lml, iters, E, batch_mean, batch_var_unbiased, a, s, rnorm)."""
-    return _EpisodeFn.apply(_BnTrunk, _Laplace, x, gamma, beta, eps, use_bn, y, sv, cls_weight, max_iter)
+    """x [B,N,D] trunk output BEFORE bn_out, N <= 127.  Returns (obj, logp, iters, e, batch_mean, batch_var_unbiased, a, s, rnorm)."""
+    return _episode(_BnTrunk, (x, gamma, beta, eps, use_bn), "laplace", (y, sv, cls_weight, max_iter))
 
 
 def dirichlet_objective(e, ytilde, noise_rows, sv, mean, cls_weight):
-    """Differentiable (in e, sv, mean) Dirichlet-likelihood objective of B episodes: returns (obj [B], logp [B,C], alpha [B,C,N], info [B,C]); arguments as
-    `mll_rownoise`, ytilde / noise_rows of `dirichlet_targets`.  One launch (two for a shared e), no host read-back."""
-    return _EpisodeFn.apply(_GivenE, _Dirichlet, e, ytilde, noise_rows, sv, mean, cls_weight)
+    """Differentiable (in e, sv, mean) Dirichlet-likelihood objective of B episodes; arguments as `mll_rownoise`, ytilde / noise_rows of `dirichlet_targets`.
+    Returns (obj, logp, alpha, info): obj [B], logp [B,C], alpha [B,C,N], info [B,C].  One launch (two for a shared e), no host read-back."""
+    return _episode(_GivenE, (e,), "dirichlet", (ytilde, noise_rows, sv, mean, cls_weight))
 
 
 def episode_loss_dirichlet(z, ytilde, noise_rows, sv, mean, cls_weight, kernel: str, lengthscale=None, offset=None, unit_rows: bool = False):
     """Dirichlet-likelihood training episode(s) z [B,N,D] (N <= 127, C <= 32): K_c = sv_c * k_c(z, z) + diag(noise_rows_c).  The linear kernels with
     D <= 64 take any N: above 127 rows (rownoise_lowrank_applies) the episode runs in feature space and E is None.
-    Returns (obj [B], logp [B,C], alpha [B,C,N], info [B,C], E)."""
-    z = _req(z, "z", 3)
-    if kernel in LINEAR_KINDS:
-        objv = _FeatureSpaceDirichlet if rownoise_lowrank_applies(z.shape[1], z.shape[2], ytilde.shape[-2], z.is_cuda) else _Dirichlet
-        return _EpisodeFn.apply(_LinearGram, objv, z, unit_rows, ytilde, noise_rows, sv, mean, cls_weight)
-    cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
-    return _EpisodeFn.apply(_ClassKernel, _Dirichlet, z, param, cmap, power, base_kind, ytilde, noise_rows, sv, mean, cls_weight)
+    Returns (obj, logp, alpha, info, e): obj [B], logp [B,C], alpha [B,C,N], info [B,C], E."""
+    return _episode(*_rows_front(z, kernel, lengthscale, offset, unit_rows), "dirichlet", (ytilde, noise_rows, sv, mean, cls_weight))
 
 
 def episode_loss_dirichlet_bn(x, gamma, beta, ytilde, noise_rows, sv, mean, cls_weight, eps: float = 1e-5, use_bn: bool = True):
     """x [B,N,D] trunk output BEFORE bn_out (float32, bfloat16 or float16), N <= 127 -- or, with D <= 64, any N: above 127 rows the episode runs in
     feature space (rownoise_lowrank_applies) and E is None.
-    Returns (obj [B], logp, alpha, info, E, batch_mean, batch_var_unbiased, a, s, rnorm)."""
-    objv = _FeatureSpaceDirichlet if x.dim() == 3 and rownoise_lowrank_applies(x.shape[1], x.shape[2], ytilde.shape[-2], x.is_cuda) else _Dirichlet
-    return _EpisodeFn.apply(_BnTrunk, objv, x, gamma, beta, eps, use_bn, ytilde, noise_rows, sv, mean, cls_weight)
+    Returns (obj, logp, alpha, info, e, batch_mean, batch_var_unbiased, a, s, rnorm)."""
+    return _episode(_BnTrunk, (x, gamma, beta, eps, use_bn), "dirichlet", (ytilde, noise_rows, sv, mean, cls_weight))
 
 
 def loo_objective(e, y, sv, mean, noise, cls_weight, jitter0: float = 1e-6, max_tries: int = 3):
     """Differentiable (in e, sv, mean, noise) leave-one-out objective of B episodes, obj[b] = sum_c cls_weight[c] loo[b,c]; arguments as `loo`.
-    Returns (obj [B], loo [B,C], alpha [B,C,N], info [B,C], jitter [B,C], mu_loo [B,C,N], var_loo [B,C,N]).  One launch, no host read-back."""
-    return _EpisodeFn.apply(_GivenE, _LooCV, e, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+    Returns (obj, logp, alpha, info, jitter, mu_loo, var_loo): obj [B], logp [B,C] (loo), alpha [B,C,N], info [B,C], jitter [B,C], mu_loo [B,C,N],
+    var_loo [B,C,N].  One launch, no host read-back."""
+    return _episode(_GivenE, (e,), "loo", (y, sv, mean, noise, cls_weight, jitter0, max_tries))
 
 
 def episode_loss_loo(z, y, sv, mean, noise, cls_weight, kernel: str, lengthscale=None, offset=None, unit_rows: bool = False,
                      jitter0: float = 1e-6, max_tries: int = 3):
     """Leave-one-out training episode(s) z [B,N,D] (N <= 127, C <= 32): K_c = sv_c * k_c(z, z) + noise_c I, every kernel of the marginal-likelihood path.
     The linear kernels with D <= 64 take any N above 128 rows (loo_lowrank_applies): the episode runs in feature space and E is None.
-    Returns (obj [B], loo [B,C], alpha [B,C,N], info, jitter [B,C], mu_loo, var_loo [B,C,N], E)."""
-    z = _req(z, "z", 3)
-    if kernel in LINEAR_KINDS:
-        objv = _FeatureSpaceLooCV if loo_lowrank_applies(z.shape[1], z.shape[2], y.shape[-2], z.is_cuda) else _LooCV
-        return _EpisodeFn.apply(_LinearGram, objv, z, unit_rows, y, sv, mean, noise, cls_weight, jitter0, max_tries)
-    cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
-    return _EpisodeFn.apply(_ClassKernel, _LooCV, z, param, cmap, power, base_kind, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+    Returns (obj, logp, alpha, info, jitter, mu_loo, var_loo, e): obj [B], logp [B,C] (loo), alpha [B,C,N], info, jitter [B,C], mu_loo, var_loo [B,C,N], E."""
+    return _episode(*_rows_front(z, kernel, lengthscale, offset, unit_rows), "loo", (y, sv, mean, noise, cls_weight, jitter0, max_tries))
 
 
 def episode_loss_loo_bn(x, gamma, beta, y, sv, mean, noise, cls_weight, eps: float = 1e-5, jitter0: float = 1e-6, max_tries: int = 3, use_bn: bool = True):
     """x [B,N,D] trunk output BEFORE bn_out (float32, bfloat16 or float16), N <= 127 -- or, with D <= 64, any N above 128 rows: the episode runs in
     feature space (loo_lowrank_applies) and E is None.
-    Returns (obj [B], loo, alpha, info, jitter, mu_loo, var_loo, E, batch_mean, batch_var_unbiased, a, s, rnorm)."""
-    objv = _FeatureSpaceLooCV if x.dim() == 3 and loo_lowrank_applies(x.shape[1], x.shape[2], y.shape[-2], x.is_cuda) else _LooCV
-    return _EpisodeFn.apply(_BnTrunk, objv, x, gamma, beta, eps, use_bn, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+    Returns (obj, logp, alpha, info, jitter, mu_loo, var_loo, e, batch_mean, batch_var_unbiased, a, s, rnorm)."""
+    return _episode(_BnTrunk, (x, gamma, beta, eps, use_bn), "loo", (y, sv, mean, noise, cls_weight, jitter0, max_tries))
 
 
 def episode_loss_class_kernel(z, y, sv, mean, noise, cls_weight, kernel: str, lengthscale=None, offset=None,
                               jitter0: float = 1e-6, max_tries: int = 3):
     """Training episode(s) z:[B,N,D] for rbf / matern / poli1 / poli2 with per-class lengthscale / offset [C], sizes of
     mll_per_class_supported().
-    Returns (obj[B], logp[B,C], alpha[B,C,N], info[B,C], jitter[B,C], E[B,C,N,N])."""
+    Returns (obj, logp, alpha, info, jitter, e): obj [B], logp [B,C], alpha [B,C,N], info [B,C], jitter [B,C], E [B,C,N,N]."""
     cmap, power, param, base_kind = _classmap_of(kernel, lengthscale, offset)
-    return _EpisodeFn.apply(_ClassKernel, _Gaussian, _req(z, "z", 3), param, cmap, power, base_kind, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+    return _episode(_ClassKernel, (_req(z, "z", 3), param, cmap, power, base_kind), "gaussian", (y, sv, mean, noise, cls_weight, jitter0, max_tries))
 
 
 def episode_loss_bn(x, gamma, beta, y, sv, mean, noise, cls_weight, eps: float = 1e-5, jitter0: float = 1e-6, max_tries: int = 3,
                     use_bn: bool = True, full: bool = False):
-    """x:[B,N,D] trunk output BEFORE bn_out (float32, bfloat16 or float16).  Returns (obj[B], logp, alpha, info, jitter, E (None when the episode ran in feature space: lowrank_applies), batch_mean[B,D],
-    batch_var_unbiased[B,D]) -- the last two feed the caller's running-statistics update -- plus, with full=True, the folded
+    """x:[B,N,D] trunk output BEFORE bn_out (float32, bfloat16 or float16).
+    Returns (obj, logp, alpha, info, jitter, e, batch_mean, batch_var_unbiased): obj [B], E (None when the episode ran in feature space: lowrank_applies),
+    batch_mean [B,D], batch_var_unbiased [B,D] -- the last two feed the caller's running-statistics update -- plus, with full=True, the folded
     affine map a, s and the row scales rnorm (zn = (a x + s) rnorm: what a caller needs to re-create the normalised features)."""
-    objv = _FeatureSpaceGaussian if lowrank_applies(x.shape[1], x.shape[2], y.shape[-2], x.shape[0], front_end=True) else _Gaussian
-    out = _EpisodeFn.apply(_BnTrunk, objv, x, gamma, beta, eps, use_bn, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+    out = _episode(_BnTrunk, (x, gamma, beta, eps, use_bn), "gaussian", (y, sv, mean, noise, cls_weight, jitter0, max_tries))
     return out if full else out[:8]
 
 
 def episode_loss_linear(z, y, sv, mean, noise, cls_weight, jitter0: float = 1e-6, max_tries: int = 3, unit_rows: bool = False):
-    """z:[B,N,D] (already bn_out'ed + normalised).  Returns (obj[B], logp, alpha, info, jitter, E).
+    """z:[B,N,D] (already bn_out'ed + normalised).  Returns (obj, logp, alpha, info, jitter, e).
     unit_rows=True: z went through F.normalize (cossim / bncossim), |z| <= 1 element-wise -- the Gram kernels may then use
     the scaled 2-way f16 split (same fp32-level accuracy, less staging work).
     D <= 64 < N where it wins (lowrank_applies: the Conv4S / Omniglot episodes -- every 420-row batch, 105-row batches from 3072 episodes): the episode runs in
     feature space and E is None -- no N x N matrix exists."""
-    objv = _FeatureSpaceGaussian if z.dim() == 3 and lowrank_applies(z.shape[1], z.shape[2], y.shape[-2], z.shape[0]) else _Gaussian
-    return _EpisodeFn.apply(_LinearGram, objv, z, unit_rows, y, sv, mean, noise, cls_weight, jitter0, max_tries)
+    return _episode(_LinearGram, (z, unit_rows), "gaussian", (y, sv, mean, noise, cls_weight, jitter0, max_tries))
+
+

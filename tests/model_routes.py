@@ -83,17 +83,27 @@ def train(dev, kernel, nb=1, n_way=5, per=5, n_support=2, d=64, logits=False, **
     return m, call
 
 
-def correct(dev, kernel, N=0, laplace=False, n_way=5, proba=None, logits=False, **kw):
-    """_correct_device (correct when N > 0) on one eval-mode test episode, n_support 2 and n_query 3; proba: also laplace_proba; logits: also get_logits."""
-    m = _model(dev, kernel, n_way, **kw)
-    x = _images(3, n_way, 5)
+def correct(dev, kernel, N=0, laplace=False, n_way=5, proba=None, logits=False, n_support=2, n_query=3, episode=True, dirichlet_proba=None, loo_accuracy=False,
+            **kw):
+    """_correct_device (correct when N > 0) on one eval-mode test episode, n_support 2 and n_query 3 unless given; proba: also laplace_proba; logits: also
+    get_logits; dirichlet_proba: also dirichlet_proba with that many samples; loo_accuracy: also loo_accuracy and what it left in _last["loo"]; episode=False:
+    only those, no _correct_device."""
+    m = _model(dev, kernel, n_way, n_support, **kw)
+    x = _images(3, n_way, n_support + n_query)
 
     def call():
         m.eval()
-        m.n_query = 3
+        m.n_query = n_query
         outs = {}
         if logits:
             outs["logits"] = m.get_logits(x)
+        if dirichlet_proba is not None:
+            outs["dirichlet_proba"] = m.dirichlet_proba(x, samples=dirichlet_proba)
+        if loo_accuracy:
+            outs["loo_accuracy"] = torch.tensor(m.loo_accuracy(x), dtype=torch.float64)
+            outs.update({"loo_" + k: v for k, v in m._last["loo"].items()})
+        if not episode:
+            return outs
         if N > 0:
             top1, count, avg_loss = m.correct(x, N=N, laplace=laplace)
             outs.update(top1=torch.tensor(top1), avg_loss=torch.tensor(avg_loss, dtype=torch.float64))
@@ -145,6 +155,8 @@ class Route:
 
 _UNFUSED = dict(DKT_FUSED_FRONTEND="0")
 _GRAPH = dict(DKT_TRAIN_GRAPH="1")
+_DIR = dict(likelihood="dirichlet")
+_LOO = dict(objective="loo")
 ROUTES = [
     Route("train-fused-bn/momentum0.1-mb1", lambda dev: train(dev, "bncossim"), "gram_bn_train_f32 mll_f32 objective_f32 gram_bn_bwd_f32 hyper_grads_f32"),
     Route("train-fused-bn/cumulative-mb3", lambda dev: train(dev, "bncossim", nb=3, momentum=None), "gram_bn_train_f32 mll_f32 objective_f32 gram_bn_bwd_f32 bn_param_grads_f32 hyper_grads_f32"),
@@ -173,6 +185,33 @@ ROUTES = [
     Route("regression-loss/rbf", lambda dev: regression(dev, "rbf"), "gram_f32 mll_f32 objective_f32 hyper_grads_f32 rbf_bwd_f32 gram_bwd_f32"),
     Route("regression-loss/spectral", lambda dev: regression(dev, "spectral"), "smk_f32 mll_f32 objective_f32 hyper_grads_f32 smk_bwd_f32"),
     Route("regression-loss/sines", lambda dev: regression(dev), "smk_task_f32 mll_f32 objective_f32 hyper_grads_f32 smk_task_bwd_f32"),
+    # the Dirichlet likelihood, the leave-one-out objective and the feature-space forms (26 rows per class: N = 130 > 128, D = 64)
+    Route("train-dirichlet/bncossim", lambda dev: train(dev, "bncossim", **_DIR), "gram_bn_train_f32 mll_rownoise_f32 objective_f32 gram_bn_bwd_f32"),
+    Route("train-dirichlet/bncossim-unfused", lambda dev: train(dev, "bncossim", **_DIR), "gram_f32 mll_rownoise_f32 objective_f32 gram_bwd_f32", env=_UNFUSED),
+    Route("train-dirichlet/rbf", lambda dev: train(dev, "rbf", **_DIR), "gram_f32 class_kernel_f32 mll_rownoise_f32 objective_f32 class_kernel_bwd_f32 gram_bwd_f32"),
+    Route("train-dirichlet/mb3", lambda dev: train(dev, "bncossim", nb=3, **_DIR), "gram_bn_train_f32 mll_rownoise_f32 objective_f32 gram_bn_bwd_f32 bn_param_grads_f32"),
+    Route("train-dirichlet-feature-space/fused", lambda dev: train(dev, "bncossim", per=26, **_DIR), "bn_stats_f32 affine_normalize_f32 rownoise_lowrank_f32 objective_f32 rownoise_lowrank_bwd_f32 normalize_bn_bwd_f32"),
+    Route("train-dirichlet-feature-space/unfused", lambda dev: train(dev, "bncossim", per=26, **_DIR), "rownoise_lowrank_f32 objective_f32 rownoise_lowrank_bwd_f32", env=_UNFUSED),
+    Route("train-loo/bncossim", lambda dev: train(dev, "bncossim", **_LOO), "gram_bn_train_f32 loo_f32 objective_f32 gram_bn_bwd_f32 hyper_grads_f32"),
+    Route("train-loo/bncossim-unfused", lambda dev: train(dev, "bncossim", **_LOO), "gram_f32 loo_f32 objective_f32 gram_bwd_f32 hyper_grads_f32", env=_UNFUSED),
+    Route("train-loo/rbf", lambda dev: train(dev, "rbf", **_LOO), "gram_f32 class_kernel_f32 loo_f32 objective_f32 class_kernel_bwd_f32 gram_bwd_f32 hyper_grads_f32"),
+    Route("train-loo/mb3", lambda dev: train(dev, "bncossim", nb=3, **_LOO), "gram_bn_train_f32 loo_f32 objective_f32 gram_bn_bwd_f32 bn_param_grads_f32 hyper_grads_f32"),
+    Route("train-loo-feature-space/fused", lambda dev: train(dev, "bncossim", per=26, **_LOO), "bn_stats_f32 affine_normalize_f32 loofs_f32 objective_f32 normalize_bn_bwd_f32 hyper_grads_f32"),
+    Route("train-loo-feature-space/unfused", lambda dev: train(dev, "bncossim", per=26, **_LOO), "loofs_f32 objective_f32 hyper_grads_f32", env=_UNFUSED),
+    Route("train-gaussian-feature-space/fused", lambda dev: train(dev, "bncossim", per=26), "bn_stats_f32 affine_normalize_f32 lowrank_gram_f32 mll_f32 lowrank_finish_f32 lowrank_bwd_f32 normalize_bn_bwd_f32 hyper_grads_f32"),
+    Route("train-gaussian-feature-space/unfused", lambda dev: train(dev, "bncossim", per=26), "lowrank_gram_f32 mll_f32 lowrank_finish_f32 lowrank_bwd_f32 hyper_grads_f32", env=_UNFUSED),
+    Route("correct-dirichlet/fused", lambda dev: correct(dev, "bncossim", **_DIR), "gram_bn_f32 mll_rownoise_f32"),
+    Route("correct-dirichlet/unfused", lambda dev: correct(dev, "bncossim", **_DIR), "gram_f32*2 mll_rownoise_f32", env=_UNFUSED),
+    Route("correct-dirichlet/rbf", lambda dev: correct(dev, "rbf", **_DIR), "gram_f32*2 class_kernel_f32*2 mll_rownoise_f32"),
+    Route("correct-dirichlet/feature-space", lambda dev: correct(dev, "bncossim", n_support=26, n_query=2, **_DIR), "rownoise_lowrank_f32 rownoise_lowrank_predict_f32"),
+    Route("dirichlet-proba/bncossim", lambda dev: correct(dev, "bncossim", episode=False, dirichlet_proba=8, **_DIR), "gram_f32*2 mll_rownoise_f32 dirichlet_proba_f32"),
+    Route("dirichlet-proba/rbf", lambda dev: correct(dev, "rbf", episode=False, dirichlet_proba=8, **_DIR), "gram_f32*3 class_kernel_f32*3 mll_rownoise_f32 dirichlet_proba_f32"),
+    Route("dirichlet-proba/feature-space", lambda dev: correct(dev, "bncossim", episode=False, dirichlet_proba=8, n_support=26, n_query=2, **_DIR), "rownoise_lowrank_f32 rownoise_lowrank_predict_f32 dirichlet_proba_f32"),
+    Route("loo-accuracy/bncossim", lambda dev: correct(dev, "bncossim", episode=False, loo_accuracy=True, **_LOO), "gram_f32 loo_f32"),
+    Route("loo-accuracy/rbf", lambda dev: correct(dev, "rbf", episode=False, loo_accuracy=True, **_LOO), "gram_f32 class_kernel_f32 loo_f32"),
+    Route("loo-accuracy/feature-space", lambda dev: correct(dev, "bncossim", episode=False, loo_accuracy=True, n_support=26, n_query=2, **_LOO), "loofs_f32"),
+    Route("correct-adapt/dirichlet", lambda dev: correct(dev, "bncossim", N=2, **_DIR), "gram_f32*4 mll_rownoise_f32*3 objective_f32*2"),
+    Route("correct-adapt/loo", lambda dev: correct(dev, "bncossim", N=2, **_LOO), "gram_f32*4 loo_f32*2 objective_f32*2 hyper_grads_f32*2 mll_f32"),
 ]
 
 
