@@ -375,7 +375,9 @@ void mll_h2_kernel(MllArgs a, const int wpg) {
             trk = wave_reduce_dpp<false>(trk);
             if (lane == 0) {
                 const bool ok = fail_at == 0;
-                a.logp[bc] = ok ? (-0.5f * quad - 0.34657359027997264f * lsum - (float)N * DKT_HALF_LOG_2PI) : qnan;
+                // explicit fmas: left to -ffp-contract the compiler fused another product in the GRAD = false instantiations than in the GRAD = true ones
+                // (fma(c, lsum, -0.5 quad) there, fma(-0.5, quad, c lsum) here), and the forward-only call's logp was an ulp off the training call's
+                a.logp[bc] = ok ? fmaf(-(float)N, DKT_HALF_LOG_2PI, fmaf(-0.5f, quad, -0.34657359027997264f * lsum)) : qnan;
                 a.jitter_used[bc] = jit;
                 a.info[bc] = (ok && kappa_high) ? -1 : fail_at;
                 if constexpr (GRAD) {
